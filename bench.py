@@ -1,6 +1,12 @@
 """bench.py — training-steps/sec of the MeshGraphNet hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+    A plain run sets up, warms up, times the K steps and prints the headline JSON line (metric, value,
+    unit, higher_is_better, dtype, ms_per_step, configuration); --dump-outputs DIR also writes what the
+    last timed step computed (dump_outputs). Everything else the benchmark measures — the sustained
+    rate, the per-class kernel profile and roofline, the standalone segment sum, the one-step MSE against
+    the reference CPU path, the CPU baseline, the fp32 Cfg B / Cfg A / Cfg C / Cfg E rows — runs only with
+    --full (where --cpu-steps, --sustain, --no-secondary, --no-mse, --no-profile select among them).
     N>1: `python bench.py --gpus N` starts its N ranks itself (torch.distributed.run as a child process,
     before anything touches the GPU) and forwards rank 0's JSON line; run under a launcher
     (python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N) it is
@@ -16,7 +22,7 @@ AdamW(wd 1e-4, β (0.9, 0.95)) → cosine-warmup LR step, exactly the reference 
 
 value = (steps completed by all ranks) / (max-over-ranks wall time of the K timed steps); each rank's
 step is one batch-8 CylinderFlow step, so value/N is the per-GPU step rate (weak scaling).
-Extra JSON fields: roofline (dominant kernel, HIP-event timed over the timed region), cpu_baseline
+Extra JSON fields with --full: roofline (dominant kernel, HIP-event timed over the timed region), cpu_baseline
 (reference-semantics CPU path = oracle, timed on this host's cores, rank 0, N=1), one_step_mse
 (GPU vs reference CPU path on held-out frames with the trained weights), kernels (per-class times).
 """
@@ -46,6 +52,13 @@ def parse():
     # start-up cost (same box: 343.9 -> 349.6 steps/s, tools/dev/r06_steps.sh)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement and check (sustained rate, "
+                         "per-class profile + roofline, one-step MSE, CPU baseline, secondary configurations); "
+                         "without it only the headline figure is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, gradients, updated parameters, "
+                         "normalizer statistics) as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=8, help="graphs per GPU")
     ap.add_argument("--mp", type=int, default=15)
     ap.add_argument("--hidden", type=int, default=128)
@@ -77,6 +90,9 @@ def parse():
     a = ap.parse_args()
     if a.fresh_batch:
         a.no_graph = True
+    if not a.full:  # a plain run measures the headline figure only
+        a.cpu_steps, a.sustain = 0, 0.0
+        a.no_secondary = a.no_mse = a.no_profile = True
     return a
 
 
@@ -235,6 +251,36 @@ def warm(a, step):
         for _ in range(a.warmup):
             step()
     torch.cuda.synchronize()
+
+
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes written by --dump-outputs, all files together
+
+
+def dump_outputs(path, loss, sim):
+    """--dump-outputs: what a caller of the timed step receives from its last call, as <path>/<name>.npy:
+    `loss` (the step's return value), `grads` (every parameter's gradient of that step, fp32, in
+    named_parameters order, flattened and concatenated), `params` (the parameters after that step's AdamW
+    update, same order), `normalizers` (the Simulator's buffers: the online normalizers' accumulators,
+    float64). Above DUMP_BUDGET bytes in all, grads and params are a fixed sample (the same seeded
+    element indices for both, sorted) whose indices are written as `sample_index`."""
+    ps = [p for _, p in sim.named_parameters()]
+    flat = lambda ts, dt: (torch.cat([t.detach().reshape(-1).to(dt) for t in ts]).cpu().numpy() if ts
+                           else np.zeros(0, dtype=np.float32))
+    arrays = {"loss": loss.detach().reshape(-1).float().cpu().numpy(),
+              "params": flat(ps, torch.float32),
+              "grads": flat([p.grad if p.grad is not None else torch.zeros_like(p) for p in ps], torch.float32),
+              "normalizers": flat(list(sim.buffers()), torch.float64)}
+    fixed = arrays["loss"].nbytes + arrays["normalizers"].nbytes
+    n = arrays["params"].size
+    fixed += 5 * 128  # the .npy headers
+    if fixed + 8 * n > DUMP_BUDGET:
+        keep = max((DUMP_BUDGET - fixed) // 16, 1)  # 4 B param + 4 B grad + 8 B index per kept element
+        idx = np.sort(np.random.default_rng(0).choice(n, size=min(keep, n), replace=False))
+        arrays["params"], arrays["grads"] = arrays["params"][idx], arrays["grads"][idx]
+        arrays["sample_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 PROFILE_SCHEDULE = ("one stream, whole chip: each kernel class timed alone (the timed replay runs the "
@@ -532,6 +578,9 @@ def main():
     dt = time.perf_counter() - t0
     ctl_ms = 1000 * (step.ctl_seconds - ctl0) / a.steps  # host gloo re-capture agreement (N > 1, graph mode)
     log("timed steps done: %.3f ms/step" % (1000 * dt / a.steps))
+    if a.dump_outputs and rank == 0:  # before anything below trains the model further
+        dump_outputs(a.dump_outputs, loss, sim)
+        log("outputs of the last timed step written to %s" % a.dump_outputs)
     # sustained rate: the same step replayed for about `sustain` more seconds (reported beside the
     # headline, never as `value`; it also keeps the GPU visibly busy for the driver's sampler)
     sus = None

@@ -6,14 +6,14 @@
 # schedule bench.py times its per-class kernels in); 3) FETCH_SIZE pass; 4) WRITE_SIZE pass; 5) SQ/GRBM
 # pass (MFMA busy cycles, wave states) — separate --pmc runs, no tracing domains, on one stream too, so a
 # PMC record describes the same launch bench.py's avg_launch_us times.
-# Outputs under gpurun_out/prof_<tag>/, plus traffic.json (per kernel instance, stamped with the
+# Outputs under $MGN_LOGDIR/prof_<tag>/ (default logs/), plus traffic.json (per kernel instance, stamped with the
 # kernel sources' hash and the workload).
 set -e
 TAG=${1:-r02}
 shift || true
 EXTRA="$*"
 export TMPDIR=/tmp
-OUT=gpurun_out/prof_$TAG
+OUT=${MGN_LOGDIR:-logs}/prof_$TAG
 mkdir -p $OUT
 ARGS="--steps 5 --warmup 3 --cpu-steps 0 --no-mse --no-profile --no-secondary --sustain 0 $EXTRA"
 WL=$(python3 bench.py --print-workload $EXTRA)
