@@ -132,6 +132,11 @@ EXPORTS = {
                                           ctypes.POINTER(MlpSaved), _vp, _i32, _vp, _i32, _vp, _vp, _sz, _vp, _sz,
                                           ctypes.POINTER(WgradReduce), _i32, ctypes.POINTER(CallOpts), _vp]),
     "mgn_debug_wave_times": (_i32, [_i32, _vp, _i32]),
+    "mgn_graph_attention_workspace_bytes": (_sz, [ctypes.POINTER(Topology), _i32, _i32, _i32]),
+    "mgn_graph_attention_forward": (_i32, [ctypes.POINTER(Topology), _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp,
+                                           _vp, _vp]),
+    "mgn_graph_attention_backward": (_i32, [ctypes.POINTER(Topology), _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32,
+                                            _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mgn_permute_rows": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "mgn_segment_sum": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "mgn_column_stats_workspace_bytes": (_sz, [_i64, _i32]),
@@ -198,7 +203,11 @@ def load(path=LIB_PATH):
             "The MGN path has no CPU fallback.")
     lib = ctypes.CDLL(path)
     for name, (res, args) in EXPORTS.items():
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:  # symbols added without an ABI bump (e.g. mgn_graph_attention_*): a stale build
+            raise RuntimeError(f"libmgn at {path} does not export {name}: it is older than these bindings, "
+                               "rebuild (python __graft_entry__.py)") from None
         fn.restype = res
         fn.argtypes = args
     if lib.mgn_abi_version() != ABI_VERSION:  # a stale build would mis-read changed signatures

@@ -930,6 +930,92 @@ class EPDFunction(torch.autograd.Function):
         return (None, None, None, None, gx, gea, None, *plan.grad_views(G))
 
 
+# --------------------------------------------------------------------------- graph attention
+class GraphAttentionFunction(torch.autograd.Function):
+    """y = adjacency-masked multi-head attention (mgn_graph_attention_forward / _backward, mgn.h) of
+    q, k, v [N, h] (fp32 or bf16; other dtypes run as fp32), which may be column slices of one buffer.
+    k = v = None: q is the packed [N, 3h] output of one q/k/v projection and gets one packed gradient.
+    Workspace, y and lse come from the caching allocator; nothing synchronises with the host."""
+
+    @staticmethod
+    def forward(ctx, topo, heads, q, k, v):
+        packed = k is None
+        src = q.detach()
+        cdt = src.dtype if src.dtype in (torch.float32, torch.bfloat16) else torch.float32
+        if packed:
+            if src.dtype != cdt or src.stride(1) != 1:
+                src = src.to(cdt).contiguous()
+            h = src.shape[1] // 3
+            qs, ks, vs = src[:, :h], src[:, h:2 * h], src[:, 2 * h:]
+        else:
+            qs, ks, vs = (t.detach().to(cdt) for t in (q, k, v))
+            if not (qs.stride(1) == ks.stride(1) == vs.stride(1) == 1 and qs.stride(0) == ks.stride(0) == vs.stride(0)):
+                qs, ks, vs = qs.contiguous(), ks.contiguous(), vs.contiguous()
+            h = qs.shape[1]
+        N, dev = qs.shape[0], qs.device
+        if N != topo.num_nodes or ks.shape != qs.shape or vs.shape != qs.shape:
+            raise ValueError(f"graph attention: q, k, v must be [{topo.num_nodes}, h], got {list(qs.shape)}, "
+                             f"{list(ks.shape)}, {list(vs.shape)}")
+        mdt = nat.mgn_dtype(cdt)
+        ld = qs.stride(0) if N > 1 else max(qs.stride(0), h)
+        y = torch.empty((N, h), dtype=cdt, device=dev)
+        lse = torch.empty((N, heads), dtype=torch.float32, device=dev)
+        nat.check(nat.lib().mgn_graph_attention_forward(
+            ctypes.byref(topo.struct), nat.ptr(qs), nat.ptr(ks), nat.ptr(vs), ld, h, heads, mdt, nat.ptr(y),
+            nat.ptr(lse), nat.stream_ptr(dev)))
+        if any(ctx.needs_input_grad):
+            ctx.topo, ctx.heads, ctx.packed, ctx.ld, ctx.mdt = topo, heads, packed, ld, mdt
+            ctx.in_dtype = q.dtype
+            ctx.state = (qs, ks, vs, y, lse)
+        return y if q.dtype == cdt else y.to(q.dtype)
+
+    @staticmethod
+    def backward(ctx, gy):
+        topo, heads = ctx.topo, ctx.heads
+        qs, ks, vs, y, lse = ctx.state
+        N, h = y.shape
+        dev = y.device
+        dy = gy.detach().to(y.dtype).contiguous()
+        L = nat.lib()
+        wsb = int(L.mgn_graph_attention_workspace_bytes(ctypes.byref(topo.struct), h, heads, ctx.mdt))
+        ws = _empty(wsb, torch.uint8, dev)
+        d = torch.empty((3, N, h), dtype=y.dtype, device=dev)
+        nat.check(L.mgn_graph_attention_backward(
+            ctypes.byref(topo.struct), nat.ptr(qs), nat.ptr(ks), nat.ptr(vs), nat.ptr(y), nat.ptr(lse), nat.ptr(dy),
+            ctx.ld, h, heads, ctx.mdt, nat.ptr(d[0]), nat.ptr(d[1]), nat.ptr(d[2]), nat.ptr(ws), wsb,
+            nat.stream_ptr(dev)))
+        ctx.state = None
+        if ctx.packed:
+            return None, None, torch.cat((d[0], d[1], d[2]), dim=1).to(ctx.in_dtype), None, None
+        return None, None, d[0].to(ctx.in_dtype), d[1].to(ctx.in_dtype), d[2].to(ctx.in_dtype)
+
+
+class FlatGradFunction(torch.autograd.Function):
+    """Identity on a module's parameters whose backward gathers their gradients into ONE flat fp32
+    buffer laid out like module.parameters() and hands back views of it — what EPDFunction's backward
+    produces natively — for models whose dense layers run as torch ops (EncodeTransformDecode): p.grad
+    become consecutive views of one buffer, so the fused AdamW and the gradient all-reduce each touch a
+    single buffer. A parameter used several times (shared q/k/v weight) arrives here already summed."""
+
+    @staticmethod
+    def forward(ctx, *params):
+        ctx.shapes = [p.shape for p in params]
+        return tuple(p.view_as(p) for p in params)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        ref = next(g for g in grads if g is not None)
+        flat = torch.cat([(g.detach() if g is not None else ref.new_zeros(s)).reshape(-1)
+                          for g, s in zip(grads, ctx.shapes)])
+        _grad_ready(flat, 0, flat.numel())
+        out, o = [], 0
+        for s in ctx.shapes:
+            n = s.numel()
+            out.append(flat[o:o + n].view(s))
+            o += n
+        return tuple(out)
+
+
 # --------------------------------------------------------------------------- GraphNetBlock
 class BlockFunction(torch.autograd.Function):
     """(x', e') = GraphNetBlock(x, edge_index, e) with edges in the CALLER's order."""

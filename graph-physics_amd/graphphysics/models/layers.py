@@ -1,9 +1,13 @@
 """Drop-in counterparts of reference graphphysics/models/layers.py for the MGN path.
 
 Same class names, constructor signatures, attributes and state_dict keys as the reference
-(RMSNorm layers.py:18-74, build_mlp 77-113, Normalizer 265-392, GraphNetBlock 630-746), so
+(RMSNorm layers.py:18-74, build_mlp 77-113, GatedMLP / build_gated_mlp 198-262, Normalizer 265-392,
+scaled_dot_product_attention / Attention / Transformer 395-627, GraphNetBlock 630-746), so
 reference checkpoints load unchanged. GraphNetBlock.forward runs on libmgn (HIP, gfx950); there
-is no CPU fallback. The transformer/GMM components of the reference are out of scope.
+is no CPU fallback. The transformer family's attention core (the reference's DGL sparse branch) runs
+on libmgn's graph-attention kernels on a HIP tensor and as a torch composition
+(sparse_attention_torch) on a CPU tensor; its dense pieces (projections, gated MLP, stand-alone
+RMSNorm) are torch ops. The GMM heads of the reference are out of scope.
 """
 import os
 from typing import Any, Dict, Optional, Tuple, Union
@@ -33,6 +37,10 @@ class RMSNorm(nn.Module):
             self.offset = nn.Parameter(torch.zeros(d))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dtype in (torch.bfloat16, torch.float16):
+            # norms are fp32 (the output already was: scale is fp32): a bf16 Linear output under autocast is
+            # normalised in fp32 on every device, as CUDA autocast's norm policy does on a HIP device
+            x = x.float()
         if self.p < 0.0 or self.p > 1.0:
             nrm, dx = x.norm(2, dim=-1, keepdim=True), self.d
         else:
@@ -203,6 +211,193 @@ class Normalizer(nn.Module):
             "_acc_sum_squared": self._acc_sum_squared,
             "name": self.name,
         }
+
+
+# --------------------------------------------------------------------------- transformer family
+ATTENTION_HEADS = (1, 2, 4, 8)  # mgn_graph_attention_* (include/mgn.h)
+ATTENTION_MAX_HIDDEN = 256
+
+
+class GatedMLP(nn.Module):
+    """GELU(linear1(x)) ⊙ linear2(x) (reference layers.py:198-233)."""
+
+    def __init__(self, in_size: int, hidden_size: int, expansion_factor: int):
+        super().__init__()
+        self.linear1 = nn.Linear(in_size, expansion_factor * hidden_size)
+        self.linear2 = nn.Linear(in_size, expansion_factor * hidden_size)
+        self.activation = nn.GELU()
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.activation(self.linear1(x)) * self.linear2(x)
+
+
+def build_gated_mlp(in_size: int, hidden_size: int, out_size: int, expansion_factor: int = 3) -> nn.Module:
+    """RMSNorm, GatedMLP, Linear — keys {0.scale, 1.linear1/2.*, 2.*} as reference layers.py:236-262."""
+    return nn.Sequential(RMSNorm(in_size),
+                         GatedMLP(in_size=in_size, hidden_size=hidden_size, expansion_factor=expansion_factor),
+                         nn.Linear(hidden_size * expansion_factor, out_size))
+
+
+def _edge_scores(q, k, edge_index, heads):
+    """s[e, b] = Σ_d (q[row_e, dH+b] / sqrt(H)) k[col_e, dH+b]: heads interleaved (feature c -> head c % H)
+    and the reference's 1/sqrt(num_heads) scale (layers.py:411, k.size(-1) of the reshaped k)."""
+    N, h = q.shape
+    row, col = edge_index[0].long(), edge_index[1].long()
+    q3 = (q / heads ** 0.5).reshape(N, h // heads, heads)
+    return (q3[row] * k.reshape(N, h // heads, heads)[col]).sum(1), row, col
+
+
+def sparse_attention_weights(q, k, edge_index, heads):
+    """[E, H] softmax weights in the caller's edge order (DGL's attn.val): the softmax runs over the
+    out-edges of each source node (row), per head; duplicate edges are separate entries."""
+    s, row, _ = _edge_scores(q, k, edge_index, heads)
+    N = q.shape[0]
+    idx = row[:, None].expand(-1, heads)
+    m = torch.full((N, heads), float("-inf"), dtype=s.dtype, device=s.device)
+    m = m.scatter_reduce(0, idx, s.detach(), "amax")  # the shift cancels: no gradient through it
+    w = torch.exp(s - m[row])
+    den = torch.zeros((N, heads), dtype=s.dtype, device=s.device).index_add(0, row, w)
+    return w / den[row]
+
+
+def sparse_attention_torch(q, k, v, edge_index, heads):
+    """Adjacency-masked multi-head attention as a differentiable composition of torch ops, on any
+    device and dtype: y[i, dH+b] = Σ_{e: row_e = i} p[e, b] v[col_e, dH+b] with p =
+    sparse_attention_weights (0 for a node without out-edges). The CPU path of Attention, the truth
+    the libmgn kernels are tested against and the baseline they are timed against."""
+    N, h = q.shape
+    p = sparse_attention_weights(q, k, edge_index, heads)
+    row, col = edge_index[0].long(), edge_index[1].long()
+    msg = p[:, None, :] * v.reshape(N, h // heads, heads)[col]
+    y = torch.zeros((N, h // heads, heads), dtype=msg.dtype, device=msg.device).index_add(0, row, msg)
+    return y.reshape(N, h)
+
+
+def graph_attention(q, k, v, edge_index, heads):
+    """sparse_attention_torch on libmgn's HIP kernels (mgn_graph_attention_forward / _backward):
+    q, k, v [N, h] fp32 or bf16 HIP tensors, possibly column slices of one [N, 3h] buffer."""
+    nat.require_device(q)
+    topo = _engine.get_topology(edge_index, q.size(0))
+    return _engine.GraphAttentionFunction.apply(topo, heads, q, k, v)
+
+
+def scaled_dot_product_attention(q, k, v, att_mask=None, return_attention: bool = False):
+    """Reference layers.py:424-457 on q, k, v of shape (N, head_dim, num_heads). att_mask: an
+    edge_index [2, E] (in place of the reference's DGL SparseMatrix) or None (the reference's dense
+    branch, as written). The attention weights are the [E, H] values of DGL's attn."""
+    if att_mask is None:
+        attn = torch.softmax((q / k.size(-1) ** 0.5) @ k.transpose(-2, -1), dim=-1)
+        y = attn @ v
+        return (y, attn) if return_attention else y
+    N, heads = q.shape[0], q.shape[-1]
+    q2, k2, v2 = q.reshape(N, -1), k.reshape(N, -1), v.reshape(N, -1)
+    if q.is_cuda:
+        y = graph_attention(q2, k2, v2, att_mask, heads)
+    elif q.dtype in (torch.bfloat16, torch.float16):
+        # as the kernels: q, k, v and y stored in the low-precision type, scores, softmax and sums in fp32
+        y = sparse_attention_torch(q2.float(), k2.float(), v2.float(), att_mask, heads).to(q.dtype)
+    else:
+        y = sparse_attention_torch(q2, k2, v2, att_mask, heads)
+    y = y.reshape(q.shape)
+    if return_attention:
+        return y, sparse_attention_weights(q2.float() if q.dtype != torch.float64 else q2,
+                                           k2.float() if k.dtype != torch.float64 else k2, att_mask, heads)
+    return y
+
+
+def _autocast(module_dtype, x):
+    """bf16 compute: the Linear layers run as under torch.autocast(bfloat16); norms, residuals and the
+    attention's softmax stay fp32 (their inputs are promoted)."""
+    if module_dtype == torch.bfloat16:
+        return torch.autocast(device_type=x.device.type, dtype=torch.bfloat16)
+    import contextlib
+
+    return contextlib.nullcontext()
+
+
+class Attention(nn.Module):
+    """Multi-head attention masked by the mesh adjacency (reference layers.py:460-545, DGL branch).
+
+    forward(x [N, input_dim], adj, return_attention=False): adj is an edge_index [2, E] tensor (the
+    reference's dglsp.spmatrix(indices=edge_index)). On a HIP tensor the attention core runs on
+    libmgn (graph_attention; no fallback), on a CPU tensor as sparse_attention_torch."""
+
+    def __init__(self, input_dim=512, output_dim=512, num_heads=4, use_proj_bias: bool = True,
+                 use_separate_proj_weight: bool = True, compute_dtype: torch.dtype = None):
+        super().__init__()
+        if num_heads not in ATTENTION_HEADS or not 1 <= output_dim <= ATTENTION_MAX_HIDDEN \
+                or output_dim % num_heads != 0:
+            raise ValueError(f"Attention(output_dim={output_dim}, num_heads={num_heads}): libmgn's graph attention "
+                             f"supports num_heads in {ATTENTION_HEADS}, output_dim <= {ATTENTION_MAX_HIDDEN} and "
+                             "output_dim divisible by num_heads")
+        self.hidden_size = output_dim
+        self.num_heads = num_heads
+        self.head_dim = output_dim // num_heads
+        self.q_proj = nn.Linear(input_dim, output_dim, bias=use_proj_bias)
+        self.k_proj = nn.Linear(input_dim, output_dim, bias=use_proj_bias)
+        self.v_proj = nn.Linear(input_dim, output_dim, bias=use_proj_bias)
+        self.proj = nn.Linear(output_dim, output_dim, bias=use_proj_bias)
+        if not use_separate_proj_weight:
+            with torch.no_grad():
+                self.k_proj.weight = self.q_proj.weight
+                self.v_proj.weight = self.q_proj.weight
+        self.compute_dtype = compute_dtype or default_compute_dtype()
+
+    def forward(self, x: torch.Tensor, adj, return_attention: bool = False):
+        N, h, H = x.size(0), self.hidden_size, self.num_heads
+        with _autocast(self.compute_dtype, x):
+            if adj is not None and x.is_cuda:
+                # one GEMM for the three projections; the kernels read q, k, v as column slices of its output
+                w = torch.cat([self.q_proj.weight, self.k_proj.weight, self.v_proj.weight])
+                b = torch.cat([self.q_proj.bias, self.k_proj.bias, self.v_proj.bias]) \
+                    if self.q_proj.bias is not None else None
+                qkv = nn.functional.linear(x, w, b)
+                topo = _engine.get_topology(adj, N)
+                y = _engine.GraphAttentionFunction.apply(topo, H, qkv, None, None)
+                attn = sparse_attention_weights(qkv[:, :h], qkv[:, h:2 * h], adj, H) if return_attention else None
+            else:
+                q, k, v = self.q_proj(x), self.k_proj(x), self.v_proj(x)
+                q, k, v = (t.reshape(N, self.head_dim, H) for t in (q, k, v))
+                if return_attention:
+                    y, attn = scaled_dot_product_attention(q, k, v, adj, return_attention=True)
+                else:
+                    y, attn = scaled_dot_product_attention(q, k, v, adj), None
+            out = self.proj(y.reshape(N, -1))
+        return (out, attn) if return_attention else out
+
+
+class Transformer(nn.Module):
+    """x = x + attention(norm1(x), adj); x = x + gated_mlp(norm2(x)) (reference layers.py:548-627; the
+    gated MLP starts with an RMSNorm of its own, so its input is normalised twice; `activation` is
+    constructed and never used, as in the reference). adj: an edge_index [2, E] tensor."""
+
+    def __init__(self, input_dim: int, output_dim: int, num_heads: int, activation_layer: torch.nn.Module = nn.ReLU,
+                 use_proj_bias: bool = True, use_separate_proj_weight: bool = True,
+                 compute_dtype: torch.dtype = None):
+        super().__init__()
+        self.compute_dtype = compute_dtype or default_compute_dtype()
+        self.attention = Attention(input_dim=input_dim, output_dim=output_dim, num_heads=num_heads,
+                                   use_proj_bias=use_proj_bias, use_separate_proj_weight=use_separate_proj_weight,
+                                   compute_dtype=self.compute_dtype)
+        self.activation = activation_layer()
+        self.norm1, self.norm2 = RMSNorm(output_dim), RMSNorm(output_dim)
+        self.gated_mlp = build_gated_mlp(in_size=output_dim, hidden_size=output_dim, out_size=output_dim)
+        self.use_adjacency = True  # the reference's HAS_DGL_SPARSE: always the sparse branch here
+
+    def set_compute_dtype(self, dtype):
+        self.compute_dtype = self.attention.compute_dtype = dtype
+        return self
+
+    def forward(self, x: torch.Tensor, adj, return_attention: bool = False):
+        attn = None
+        with _autocast(self.compute_dtype, x):
+            if return_attention:
+                x_, attn = self.attention(self.norm1(x), adj, return_attention)
+                x = x + x_
+            else:
+                x = x + self.attention(self.norm1(x), adj, return_attention)
+            x = x + self.gated_mlp(self.norm2(x))
+        return (x, attn) if return_attention else x
 
 
 class GraphNetBlock(nn.Module):

@@ -1,4 +1,5 @@
-"""Drop-in EncodeProcessDecode (reference graphphysics/models/processors.py:27-137) on libmgn.
+"""Drop-in EncodeProcessDecode and EncodeTransformDecode (reference graphphysics/models/processors.py:27-137,
+140-277) on libmgn.
 
 Constructor, attributes (.K, .d, .temperature, .hidden_size, .only_processor, .use_diagonal) and
 state_dict keys (nodes_encoder.*, edges_encoder.*, decode_module.*, processor_list.{i}.*) match the
@@ -9,13 +10,18 @@ autograd node on HIP kernels (gfx950); the GMM decoder heads are out of scope
 
 Extra (optional) keyword: compute_dtype — torch.float32 (exact-fp32 MFMA, default) or
 torch.bfloat16 (bf16 storage, fp32 accumulation); also settable via GRAPHPHYSICS_MGN_DTYPE.
+
+EncodeTransformDecode (configs with "type": "transformer") is the reference's DGL branch: nodes_encoder,
+Transformer blocks whose attention is masked by the mesh adjacency, decode_module; it reads no
+edge_attr. The attention core runs on libmgn's graph-attention kernels; the dense layers are torch ops.
 """
 import torch
 import torch.nn as nn
 
 from graphphysics import _native as nat
 from graphphysics.models import _engine
-from graphphysics.models.layers import GraphNetBlock, build_mlp, default_compute_dtype
+from graphphysics.models.layers import (ATTENTION_HEADS, ATTENTION_MAX_HIDDEN, GraphNetBlock, Transformer, _autocast,
+                                        build_mlp, default_compute_dtype)
 
 
 class EncodeProcessDecode(nn.Module):
@@ -76,3 +82,80 @@ class EncodeProcessDecode(nn.Module):
         plan = self._get_plan()
         return _engine.EPDFunction.apply(plan, nat.mgn_dtype(self.compute_dtype), self.only_processor,
                                          torch.is_grad_enabled(), x, edge_attr, topo, *plan.params)
+
+
+class EncodeTransformDecode(nn.Module):
+    """Reference processors.py:140-277 (constructor, attributes, state_dict keys nodes_encoder.*,
+    decode_module.*, processor_list.{i}.{attention.{q,k,v}_proj, attention.proj, norm1, norm2,
+    gated_mlp}.*; modules created in the reference's order). forward(graph) reads graph.x and
+    graph.edge_index (the adjacency the reference wraps in a DGL sparse matrix). On HIP tensors the
+    attention core runs on libmgn (no fallback); on CPU tensors as a torch composition.
+
+    compute_dtype (keyword / set_compute_dtype): torch.float32 — everything fp32; torch.bfloat16 — the
+    Linear layers run as under torch.autocast(bfloat16), q, k, v, y and their gradients are bf16 for the
+    kernels, norms, residuals and softmax are fp32, master weights and gradients fp32."""
+
+    def __init__(self, message_passing_num: int, node_input_size: int, output_size: int, hidden_size: int = 128,
+                 num_heads: int = 4, only_processor: bool = False, use_proj_bias: bool = True,
+                 use_separate_proj_weight: bool = True, num_mixture_components: int = 0,
+                 temperature: float = None, use_diagonal: bool = True, compute_dtype: torch.dtype = None):
+        super().__init__()
+        if num_mixture_components != 0:
+            raise NotImplementedError("GMM decoder heads are outside the MI355X MGN hot path")
+        if num_heads not in ATTENTION_HEADS or not 1 <= hidden_size <= ATTENTION_MAX_HIDDEN \
+                or hidden_size % num_heads != 0:
+            raise ValueError(f"EncodeTransformDecode(hidden_size={hidden_size}, num_heads={num_heads}): libmgn's "
+                             f"graph attention supports num_heads in {ATTENTION_HEADS}, hidden_size <= "
+                             f"{ATTENTION_MAX_HIDDEN} and hidden_size divisible by num_heads")
+        self.hidden_size = hidden_size
+        self.only_processor = only_processor
+        self.use_diagonal = use_diagonal
+        self.d = output_size
+        self.K = num_mixture_components
+        self.temperature = temperature
+        self.message_passing_num = message_passing_num
+        self.compute_dtype = compute_dtype or default_compute_dtype()
+        if not self.only_processor:
+            self.nodes_encoder = build_mlp(node_input_size, hidden_size, hidden_size)
+            self.decode_module = build_mlp(hidden_size, hidden_size, output_size, layer_norm=False)
+        self.processor_list = nn.ModuleList(
+            [Transformer(input_dim=hidden_size, output_dim=hidden_size, num_heads=num_heads,
+                         use_proj_bias=use_proj_bias, use_separate_proj_weight=use_separate_proj_weight,
+                         compute_dtype=self.compute_dtype) for _ in range(message_passing_num)])
+        self._named = None
+        _engine.flatten_parameters(self)
+
+    # parameters live in one flat fp32 buffer (a shared q/k/v weight once); re-home them after .to()/.cuda()
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        _engine.flatten_parameters(self)
+        self._named = None
+        return out
+
+    def set_compute_dtype(self, dtype):
+        self.compute_dtype = dtype
+        for blk in self.processor_list:
+            blk.set_compute_dtype(dtype)
+        return self
+
+    def _run(self, graph) -> torch.Tensor:
+        x, edge_index = graph.x, graph.edge_index
+        with _autocast(self.compute_dtype, x):
+            if not self.only_processor:
+                x = self.nodes_encoder(x)
+            for block in self.processor_list:
+                x = block(x, edge_index)
+            if not self.only_processor:
+                x = self.decode_module(x)
+        return x.to(graph.x.dtype) if x.dtype != graph.x.dtype else x
+
+    def forward(self, graph, _flat: bool = True) -> torch.Tensor:
+        if self._named is None:
+            self._named = list(self.named_parameters())
+        if not (_flat and torch.is_grad_enabled() and any(p.requires_grad for _, p in self._named)):
+            return self._run(graph)
+        # the parameters pass through one identity node whose backward lays their gradients out in one
+        # flat buffer (module.parameters() order), as EncodeProcessDecode's backward does
+        vals = _engine.FlatGradFunction.apply(*(p for _, p in self._named))
+        return torch.func.functional_call(self, {n: v for (n, _), v in zip(self._named, vals)}, (graph,),
+                                          {"_flat": False})

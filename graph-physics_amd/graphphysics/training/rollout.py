@@ -92,7 +92,7 @@ class Rollout:
     def _record(self, batch):
         dev = batch.x.device
         self._sx, self._sy = batch.x.clone(), batch.y.clone()
-        self._sea = batch.edge_attr.clone()
+        self._sea = batch.edge_attr.clone() if batch.edge_attr is not None else None  # transformer models: none
         self._sei = batch.edge_index
         self._last = self.last_prediction.clone()
         self._lastp = self.last_previous.clone() if self.use_prev else None
@@ -140,7 +140,8 @@ class Rollout:
             else:
                 self._sx.copy_(batch.x)
                 self._sy.copy_(batch.y)
-                self._sea.copy_(batch.edge_attr)
+                if self._sea is not None:
+                    self._sea.copy_(batch.edge_attr)
                 self._last.copy_(self.last_prediction)
                 if self.use_prev:
                     self._lastp.copy_(self.last_previous)

@@ -238,8 +238,9 @@ class TrainStep:
             self._raised(ex)
             raise
         extra = {k: getattr(b, k) for k in ("pos",) if getattr(b, k, None) is not None}
-        self.batch = Data(x=b.x.clone(), y=b.y.clone(), edge_attr=b.edge_attr.clone(), edge_index=b.edge_index,
-                          **extra)
+        # edge_attr None: a model that reads no edge features (EncodeTransformDecode)
+        ea = b.edge_attr.clone() if b.edge_attr is not None else None
+        self.batch = Data(x=b.x.clone(), y=b.y.clone(), edge_attr=ea, edge_index=b.edge_index, **extra)
         snap = self._snapshot()
         # the warm-up steps are undone on a bad batch, so is the divergence mark one of them may set
         # (ADVICE r04): the recovery step below must run, and only ITS error marks the replicas
@@ -305,11 +306,13 @@ class TrainStep:
         if b is st["batch"] and all(getattr(b, k) is st[k] for k in ("x", "y", "edge_attr", "edge_index")) \
                 and b.edge_index._version == st["ei_version"]:
             return
+        keys = [k for k in ("x", "y", "edge_attr") if st[k] is not None]
         same = b.edge_index is st["edge_index"] and b.edge_index._version == st["ei_version"] and all(
-            getattr(b, k).shape == st[k].shape and getattr(b, k).dtype == st[k].dtype for k in ("x", "y", "edge_attr"))
+            getattr(b, k) is not None and getattr(b, k).shape == st[k].shape and getattr(b, k).dtype == st[k].dtype
+            for k in keys) and (st["edge_attr"] is not None or b.edge_attr is None)
         if same:
             with torch.no_grad():
-                for k in ("x", "y", "edge_attr"):
+                for k in keys:
                     if getattr(b, k) is not st[k]:
                         st[k].copy_(getattr(b, k))
             self.batch = st["batch"]

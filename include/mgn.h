@@ -369,6 +369,37 @@ int mgn_block_backward_wgrad(const mgn_topology* t, const mgn_mlp* edge, const m
                              float* edge_grads, float* node_grads, void* ws, size_t ws_bytes,
                              mgn_stream_t stream);
 
+/* ---------------------------------------------------------------- sparse graph attention */
+/* The attention core of the reference's Transformer block, DGL branch (layers.py:395-457: bsddmm,
+ * SparseMatrix.softmax, bspmm over the mesh adjacency; Attention.forward 503-545 reshapes to
+ * (N, head_dim, num_heads)), N nodes, hidden features, H heads, row = edge_index[0], col = edge_index[1]:
+ *   s[e,b] = (1/sqrt(H)) Σ_d q[row_e, dH+b] k[col_e, dH+b]    feature c is component c / H of head c % H;
+ *                                                            the scale is 1/sqrt(H), as the reference's
+ *   p[e,b] = exp(s[e,b]) / Σ_{e': row_e' = row_e} exp(s[e',b])  softmax per source node and head; duplicate
+ *                                                            edges are separate entries
+ *   y[i, dH+b] = Σ_{e: row_e = i} p[e,b] v[col_e, dH+b]        0 for a node without out-edges
+ * q, k, v: [N, hidden] with row stride ld elements (they may be column slices of one [N, 3 hidden]
+ * projection output); y, dy, dq, dk, dv: dense [N, hidden]; all of storage type dtype (MGN_F32 |
+ * MGN_BF16). Scores, softmax and every sum are fp32. lse [N, H] fp32 = log Σ exp(s) per (node, head), 0
+ * without out-edges; y and lse are all the backward needs from the forward. Supported: heads 1, 2, 4, 8,
+ * hidden % heads == 0, hidden <= 256; anything else is a nonzero status before any launch. The added
+ * symbols do not change MGN_ABI_VERSION (no existing signature changed); MGN_HAS_GRAPH_ATTENTION marks
+ * headers that declare them.
+ * Backward: two passes without atomics — grouped by source node (dq; p and dP = Σ_d dy v of every edge
+ * and δ = Σ_e p dP of every node into ws), then by target node in target-sorted order (dk, dv, with
+ * dS = p (dP − δ)). δ is summed from the edges, not as Σ_d dy y from the stored (in bf16 rounded) y, so
+ * the y argument is not read. ws: mgn_graph_attention_workspace_bytes (2 H floats per edge + H floats
+ * per node), scratch. */
+#define MGN_HAS_GRAPH_ATTENTION 1
+size_t mgn_graph_attention_workspace_bytes(const mgn_topology* t, int32_t hidden, int32_t heads, int32_t dtype);
+int mgn_graph_attention_forward(const mgn_topology* t, const void* q, const void* k, const void* v,
+                                int64_t ld, int32_t hidden, int32_t heads, int32_t dtype,
+                                void* y, float* lse /* [N, heads] */, mgn_stream_t stream);
+int mgn_graph_attention_backward(const mgn_topology* t, const void* q, const void* k, const void* v,
+                                 const void* y, const float* lse, const void* dy, int64_t ld,
+                                 int32_t hidden, int32_t heads, int32_t dtype,
+                                 void* dq, void* dk, void* dv, void* ws, size_t ws_bytes, mgn_stream_t stream);
+
 /* ---------------------------------------------------------------- primitives */
 /* out[k,:] = in[idx[k],:] (gather), or out[idx[k],:] = in[k,:] when scatter != 0. */
 int mgn_permute_rows(const void* in, void* out, const int32_t* idx, int64_t rows, int32_t cols,
