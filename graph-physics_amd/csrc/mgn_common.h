@@ -112,6 +112,15 @@ __host__ __device__ __forceinline__ int cdiv(int a, int b) { return (a + b - 1) 
 __host__ __device__ __forceinline__ int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 __host__ __device__ __forceinline__ int rup(int a, int b) { return cdiv(a, b) * b; }
 
+// --------------------------------------------------------------------------- loss row mask
+// 1 when node_type[r * ld] (a float column, e.g. a strided view of x) is an integer t < 32 with bit t of
+// tmask set, else 0: the row mask of the masked losses (mgn_masked_mse, mgn_gmm_nll_diag).
+__device__ __forceinline__ float type_mask_of(const float* nt, int64_t ld, int64_t r, unsigned tmask) {
+    const float v = nt[r * ld];
+    const int t = (int)v;
+    return (v == (float)t && t >= 0 && t < 32 && ((tmask >> t) & 1u)) ? 1.f : 0.f;
+}
+
 // --------------------------------------------------------------------------- packed weights
 // Forward fragments of W[n][k] (nn.Linear weight [out, in]):
 //   pack[((nt*KS + ks)*64 + lane)*VEC + v] = W[nt*16 + (lane&15)][ks*KSTEP + VEC*(lane>>4) + v]

@@ -454,13 +454,7 @@ __global__ __launch_bounds__(256) void normalizer_apply(const float* __restrict_
 }
 
 // Masked L2 loss (reference utils/loss.py:10-65 in its masked_mse form): one block, rows strided
-// over the threads, fixed-order tree: deterministic.
-__device__ __forceinline__ float type_mask_of(const float* nt, int64_t ld, int64_t r, unsigned tmask) {
-    const float v = nt[r * ld];
-    const int t = (int)v;
-    return (v == (float)t && t >= 0 && t < 32 && ((tmask >> t) & 1u)) ? 1.f : 0.f;
-}
-
+// over the threads, fixed-order tree: deterministic. Row mask: type_mask_of (mgn_common.h).
 // partial sums per block (fixed row range, strided threads, LDS tree) -> part[block] = {Σ m·err, Σ m}
 constexpr int MSE_BLOCKS = 64;
 __global__ __launch_bounds__(256) void masked_mse_partial(const float* __restrict__ pred,

@@ -154,6 +154,10 @@ EXPORTS = {
     "mgn_masked_mse_workspace_bytes": (_sz, [_i64]),
     "mgn_masked_mse": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mgn_masked_mse_backward": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _u32, _vp, _vp, _vp, _vp]),
+    "mgn_gmm_nll_workspace_bytes": (_sz, [_i64]),
+    "mgn_gmm_nll_diag": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _i64, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mgn_gmm_nll_diag_backward": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _i64, _u32, _vp, _vp, _vp, _vp]),
+    "mgn_gmm_sample_diag": (_i32, [_vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "mgn_adamw": (_i32, [_vp, _vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, _dbl, _dbl, _i64, _vp]),
     "mgn_adamw_dev": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _dbl, _dbl, _dbl, _dbl, _vp, _vp]),
     "mgn_adamw_dev2": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _dbl, _dbl, _dbl, _dbl, _vp, _i32, _vp]),

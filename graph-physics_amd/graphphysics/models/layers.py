@@ -7,7 +7,9 @@ reference checkpoints load unchanged. GraphNetBlock.forward runs on libmgn (HIP,
 is no CPU fallback. The transformer family's attention core (the reference's DGL sparse branch) runs
 on libmgn's graph-attention kernels on a HIP tensor and as a torch composition
 (sparse_attention_torch) on a CPU tensor; its dense pieces (projections, gated MLP, stand-alone
-RMSNorm) are torch ops. The GMM heads of the reference are out of scope.
+RMSNorm) are torch ops. DiagonalGMMHead (157-195) is the mixture-density decoder of
+EncodeTransformDecode: two Linears (torch ops); its loss and sampler run on libmgn (utils/loss.py
+masked_gmm_nll, models/simulator.py sample_gmm_diagonal). The full-covariance GMMHead is out of scope.
 """
 import os
 from typing import Any, Dict, Optional, Tuple, Union
@@ -61,6 +63,25 @@ def build_mlp(in_size: int, hidden_size: int, out_size: int, nb_of_layers: int =
     if layer_norm:
         mods.append(RMSNorm(out_size))
     return nn.Sequential(*mods)
+
+
+class DiagonalGMMHead(nn.Module):
+    """Parameters of a K-component Gaussian mixture with diagonal covariances (reference
+    layers.py:157-195): forward(x [N, input_dim]) -> [N, K(2d+1)], component k = [logit, d means,
+    d log-stds]. `temperature` scales the standard deviations in the loss and the sampler. Keys
+    pre_proj.{weight,bias}, proj.{weight,bias}, created in the reference's order."""
+
+    def __init__(self, input_dim: int, d: int, num_components: int, temperature: float = 1.0):
+        super().__init__()
+        self.d = d
+        self.K = num_components
+        self.temperature = temperature
+        self.per_component = 2 * d + 1
+        self.pre_proj = nn.Linear(input_dim, input_dim)
+        self.proj = nn.Linear(input_dim, self.K * self.per_component)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.proj(self.pre_proj(x))
 
 
 class Normalizer(nn.Module):

@@ -5,8 +5,9 @@ Constructor, attributes (.K, .d, .temperature, .hidden_size, .only_processor, .u
 state_dict keys (nodes_encoder.*, edges_encoder.*, decode_module.*, processor_list.{i}.*) match the
 reference, and modules are created in the reference's order so torch.manual_seed gives the same
 initial weights. forward(graph) runs encoders, the MP GraphNetBlocks and the decoder as one
-autograd node on HIP kernels (gfx950); the GMM decoder heads are out of scope
-(num_mixture_components must be 0).
+autograd node on HIP kernels (gfx950). Its decoder is part of the fused engine plan, so the GMM
+decoder heads are out of scope there (num_mixture_components must be 0); EncodeTransformDecode
+builds the diagonal mixture head (DiagonalGMMHead) when num_mixture_components > 0.
 
 Extra (optional) keyword: compute_dtype — torch.float32 (exact-fp32 MFMA, default) or
 torch.bfloat16 (bf16 storage, fp32 accumulation); also settable via GRAPHPHYSICS_MGN_DTYPE.
@@ -20,8 +21,8 @@ import torch.nn as nn
 
 from graphphysics import _native as nat
 from graphphysics.models import _engine
-from graphphysics.models.layers import (ATTENTION_HEADS, ATTENTION_MAX_HIDDEN, GraphNetBlock, Transformer, _autocast,
-                                        build_mlp, default_compute_dtype)
+from graphphysics.models.layers import (ATTENTION_HEADS, ATTENTION_MAX_HIDDEN, DiagonalGMMHead, GraphNetBlock,
+                                        Transformer, _autocast, build_mlp, default_compute_dtype)
 
 
 class EncodeProcessDecode(nn.Module):
@@ -31,7 +32,8 @@ class EncodeProcessDecode(nn.Module):
                  use_diagonal: bool = True, compute_dtype: torch.dtype = None):
         super().__init__()
         if num_mixture_components != 0:
-            raise NotImplementedError("GMM decoder heads are outside the MI355X MGN hot path")
+            raise NotImplementedError("GMM decoder heads on EncodeProcessDecode are not implemented: its decoder is "
+                                      "part of the fused engine plan (EncodeTransformDecode has the diagonal head)")
         self.only_processor = only_processor
         self.hidden_size = hidden_size
         self.use_diagonal = use_diagonal
@@ -93,15 +95,30 @@ class EncodeTransformDecode(nn.Module):
 
     compute_dtype (keyword / set_compute_dtype): torch.float32 — everything fp32; torch.bfloat16 — the
     Linear layers run as under torch.autocast(bfloat16), q, k, v, y and their gradients are bf16 for the
-    kernels, norms, residuals and softmax are fp32, master weights and gradients fp32."""
+    kernels, norms, residuals and softmax are fp32, master weights and gradients fp32.
+
+    num_mixture_components = K > 0 (with use_diagonal=True and a temperature): decode_module is a
+    DiagonalGMMHead and forward returns the mixture parameters [N, K(2·output_size+1)] in fp32 (its two
+    Linears under the same autocast as the rest); train it with utils.loss.masked_gmm_nll, sample it with
+    models.simulator.sample_gmm_diagonal (Simulator.forward does in evaluation mode). NotImplementedError:
+    temperature=None (the reference builds such a model, but its first loss or sample fails on
+    tensor * None) and use_diagonal=False (the reference's own training and evaluation paths always use
+    the diagonal loss and sampler, so its full-covariance head cannot be trained there either)."""
 
     def __init__(self, message_passing_num: int, node_input_size: int, output_size: int, hidden_size: int = 128,
                  num_heads: int = 4, only_processor: bool = False, use_proj_bias: bool = True,
                  use_separate_proj_weight: bool = True, num_mixture_components: int = 0,
                  temperature: float = None, use_diagonal: bool = True, compute_dtype: torch.dtype = None):
         super().__init__()
-        if num_mixture_components != 0:
-            raise NotImplementedError("GMM decoder heads are outside the MI355X MGN hot path")
+        if num_mixture_components < 0:
+            raise ValueError(f"num_mixture_components={num_mixture_components} must be >= 0")
+        if num_mixture_components > 0 and temperature is None:
+            raise NotImplementedError("a mixture head needs a temperature: the reference builds the model with "
+                                      "temperature=None, but its loss and its sampler then fail on tensor * None")
+        if num_mixture_components > 0 and not use_diagonal:
+            raise NotImplementedError("the full-covariance GMMHead (use_diagonal=False) is not implemented: the "
+                                      "reference trains and samples every mixture model with the diagonal loss "
+                                      "and sampler, which do not fit its parameter layout")
         if num_heads not in ATTENTION_HEADS or not 1 <= hidden_size <= ATTENTION_MAX_HIDDEN \
                 or hidden_size % num_heads != 0:
             raise ValueError(f"EncodeTransformDecode(hidden_size={hidden_size}, num_heads={num_heads}): libmgn's "
@@ -117,7 +134,10 @@ class EncodeTransformDecode(nn.Module):
         self.compute_dtype = compute_dtype or default_compute_dtype()
         if not self.only_processor:
             self.nodes_encoder = build_mlp(node_input_size, hidden_size, hidden_size)
-            self.decode_module = build_mlp(hidden_size, hidden_size, output_size, layer_norm=False)
+            if num_mixture_components == 0:
+                self.decode_module = build_mlp(hidden_size, hidden_size, output_size, layer_norm=False)
+            else:
+                self.decode_module = DiagonalGMMHead(hidden_size, output_size, num_mixture_components, temperature)
         self.processor_list = nn.ModuleList(
             [Transformer(input_dim=hidden_size, output_dim=hidden_size, num_heads=num_heads,
                          use_proj_bias=use_proj_bias, use_separate_proj_weight=use_separate_proj_weight,

@@ -4,7 +4,8 @@ Same constructor, attributes and forward contract: forward(inputs) ->
 (network_output, target_delta_normalized, outputs-or-None). The per-step preamble (target delta,
 one-hot node type, three online Normalizers) is O(N+E) element-wise torch work on the device; the
 Normalizers never synchronise with the host. The wrapped model is the libmgn
-EncodeProcessDecode. GMM sampling (num_mixture_components > 0) is out of scope.
+EncodeProcessDecode or EncodeTransformDecode. With a mixture head (model.K != 0) the evaluation
+forward draws one sample per node (sample_gmm_diagonal, reference simulator.py:13-57) on libmgn.
 """
 import os
 from typing import Optional, Tuple
@@ -15,6 +16,50 @@ import torch.nn as nn
 from graphphysics.models.layers import Normalizer
 from graphphysics.utils.data import Data
 from graphphysics.utils.nodetype import NodeType
+
+
+def sample_gmm_diagonal(network_output: torch.Tensor, d: int, K: int, temperature: float = 1.0,
+                        u: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One draw per node from the diagonal mixture network_output [N, K(2d+1)] describes (reference
+    simulator.py:13-57) -> [N, d]. Deterministic given its noise: with a = softmax(logit), the component
+    is the smallest k whose running sum of a exceeds u[n] (the last one catches the rest), and the sample
+    is mean_k + temperature · exp(log_std_k) · z[n]. u [N] ~ U[0, 1) and z [N, d] ~ N(0, 1) default to
+    torch.rand / torch.randn on the output's device: ordinary torch calls, so inside a captured hipGraph
+    the generator advances with every replay.
+
+    The distribution is the reference's; the draws are not: the reference picks the component with
+    torch.multinomial, which consumes the random stream differently, so the same seed gives other samples.
+    No data-dependent shapes, no Python loop over components, no host synchronisation. A HIP fp32 input
+    (1 <= K <= 16, 1 <= d <= 8) runs libmgn's mgn_gmm_sample_diag; anything else a torch composition of
+    the same rule (cumsum, comparison, gather)."""
+    from graphphysics.utils.loss import GMM_MAX_COMPONENTS, GMM_MAX_DIM
+
+    N = network_output.shape[0]
+    if network_output.dim() != 2 or network_output.shape[1] != K * (2 * d + 1):
+        raise ValueError(f"sample_gmm_diagonal: network_output {tuple(network_output.shape)} does not hold K={K} "
+                         f"components of 2·{d}+1 parameters")
+    dev, dt = network_output.device, network_output.dtype
+    u = torch.rand(N, device=dev, dtype=dt) if u is None else u.to(dev, dt).reshape(N)
+    z = torch.randn(N, d, device=dev, dtype=dt) if z is None else z.to(dev, dt).reshape(N, d)
+    if network_output.is_cuda and dt == torch.float32 and 1 <= K <= GMM_MAX_COMPONENTS and 1 <= d <= GMM_MAX_DIM:
+        from graphphysics import _native as nat
+
+        net, u, z = network_output.detach().contiguous(), u.contiguous(), z.contiguous()
+        out = torch.empty(N, d, dtype=dt, device=dev)
+        nat.check(nat.lib().mgn_gmm_sample_diag(nat.ptr(net), N, d, K, float(temperature), nat.ptr(u), nat.ptr(z),
+                                                nat.ptr(out), nat.stream_ptr(dev)))
+        return out
+    return sample_gmm_diagonal_torch(network_output, d, K, temperature, u, z)
+
+
+def sample_gmm_diagonal_torch(network_output, d, K, temperature, u, z):
+    """sample_gmm_diagonal's rule as a torch composition on any device and dtype, given its noise."""
+    N = network_output.shape[0]
+    net = network_output.reshape(N, K, 2 * d + 1)
+    cdf = torch.cumsum(torch.softmax(net[..., 0], dim=-1), dim=-1)
+    comp = (cdf <= u[:, None]).sum(dim=-1).clamp(max=K - 1)  # the first k with cdf_k > u; none: the last
+    chosen = torch.gather(net, 1, comp[:, None, None].expand(N, 1, 2 * d + 1)).squeeze(1)
+    return chosen[:, 1:1 + d] + torch.exp(chosen[:, 1 + d:]) * temperature * z
 
 
 class Simulator(nn.Module):
@@ -187,8 +232,8 @@ class Simulator(nn.Module):
         net = self.model(graph)
         if self.training:
             return net, tdn, None
-        if self.model.K != 0:
-            raise NotImplementedError("GMM sampling is outside the MI355X MGN hot path")
+        if self.model.K != 0:  # one sample per node from the mixture the head describes
+            net = sample_gmm_diagonal(net, d=self.model.d, K=self.model.K, temperature=self.model.temperature)
         return net, tdn, self._build_outputs(inputs=inputs, network_output=net)
 
     def freeze_all(self) -> None:

@@ -3,7 +3,9 @@
 Semantics = the reference's LightningModule.training_step + Lightning automatic optimisation
 (reference graphphysics/training/lightning_module.py:111-122, 275-292): Simulator train forward
 (normalizer accumulation, one-hot, EncodeProcessDecode) → masked L2 loss over NORMAL ∪ OUTFLOW
-nodes → backward → AdamW → cosine-warmup LR step (scheduler.py:41-67).
+nodes (a model with a mixture head, model.K != 0: the masked negative log-likelihood of its diagonal
+Gaussian mixture, as the reference's LightningModule.__init__ chooses its loss) → backward → AdamW →
+cosine-warmup LR step (scheduler.py:41-67).
 
 Captured mode (single process): the whole forward + backward + AdamW launch sequence (~140 kernels)
 is recorded once into a hipGraph and replayed; per step the host only writes {lr, step} to the
@@ -48,7 +50,7 @@ import torch.distributed as dist
 
 from graphphysics import _native as nat
 from graphphysics.training.distributed import GradBuckets, allreduce_gradients, flat_grad_buffer
-from graphphysics.utils.loss import masked_mse
+from graphphysics.utils.loss import masked_gmm_nll, masked_mse
 from graphphysics.utils.nodetype import NodeType
 
 
@@ -123,6 +125,10 @@ class TrainStep:
 
     def _loss(self):
         net, tdn, _ = self.sim(self.batch)
+        model = self.sim.model
+        if getattr(model, "K", 0) != 0:
+            return masked_gmm_nll(tdn, net, self.node_type, self.masks, model.d, model.K, model.temperature,
+                                  count=self._count)
         return masked_mse(tdn, net, self.node_type, self.masks, count=self._count)
 
     def _prologue(self):

@@ -482,6 +482,33 @@ int mgn_masked_mse_backward(const float* pred, const float* target, int64_t rows
                             const float* node_type, int64_t nt_ld, uint32_t type_mask, const float* count,
                             const float* grad_loss, float* grad, mgn_stream_t stream);
 
+/* Diagonal Gaussian-mixture head (reference layers.py:157-195, utils/loss.py:111-199,
+ * models/simulator.py:13-57) in a masked form without data-dependent shapes. params [rows, K(2d+1)]
+ * row-major fp32: component k of a row is [logit, mean_0..mean_{d-1}, log_std_0..log_std_{d-1}].
+ * With a = softmax(logit), s = temperature · exp(log_std),
+ *   lc_k = Σ_j −½ (2 log(s + 1e-12) + (target_j − mean_kj)² / (s² + 1e-12) + log 2π)
+ *   L    = logsumexp_k (log(a_k + 1e-12) + lc_k)                     (maximum subtracted)
+ * *loss = −Σ_r m_r L_r / c, m as in mgn_masked_mse, c = *count when given, else Σ m (written to
+ * *count_out if non-null); c == 0: the loss and every gradient are 0. Per-block partial sums in a fixed
+ * order and a single-wave final pass, no atomics: bit-reproducible. Backward (one launch, recomputes the
+ * row, written not accumulated): grad [rows, K(2d+1)] = (*grad_loss or 1) · d loss / d params, zero
+ * rows where m = 0. Sampler: the component is the smallest k whose running sum of a exceeds u[r] (the
+ * last one catches the rest), out[r, j] = mean_kj + temperature · exp(log_std_kj) · z[r, j].
+ * Supported: 1 <= K <= 16, 1 <= d <= 8; anything else is a nonzero status before any launch. The added
+ * symbols do not change MGN_ABI_VERSION; MGN_HAS_GMM marks headers that declare them. */
+#define MGN_HAS_GMM 1
+size_t mgn_gmm_nll_workspace_bytes(int64_t rows);
+int mgn_gmm_nll_diag(const float* params, const float* target /* [rows, d] */, int64_t rows, int32_t d, int32_t K,
+                     float temperature, const float* node_type, int64_t nt_ld, uint32_t type_mask,
+                     const float* count, float* loss, float* count_out, void* ws, size_t ws_bytes,
+                     mgn_stream_t stream);
+int mgn_gmm_nll_diag_backward(const float* params, const float* target, int64_t rows, int32_t d, int32_t K,
+                              float temperature, const float* node_type, int64_t nt_ld, uint32_t type_mask,
+                              const float* count, const float* grad_loss, float* grad, mgn_stream_t stream);
+int mgn_gmm_sample_diag(const float* params, int64_t rows, int32_t d, int32_t K, float temperature,
+                        const float* u /* [rows] */, const float* z /* [rows, d] */, float* out /* [rows, d] */,
+                        mgn_stream_t stream);
+
 /* torch.optim.AdamW semantics (decoupled weight decay p *= 1 - lr*wd, bias-corrected moments,
  * denominator sqrt(v)/sqrt(1-beta2^t) + eps), fp32, over n contiguous elements. */
 int mgn_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
