@@ -71,6 +71,14 @@ class PackJob(ctypes.Structure):
                 ("n_src", _i32), ("k_src", _i32), ("kb_src", _i32), ("kb_pad", _i32), ("reserved", _i32)]
 
 
+MGN_FEED_MAX_RANGES = 4
+
+
+class FeedRanges(ctypes.Structure):
+    """mgn_feed_ranges: the noisy column ranges of mgn_feed_batch, passed by value (mgn.h)."""
+    _fields_ = [("n", _i32), ("start", _i32 * MGN_FEED_MAX_RANGES), ("end", _i32 * MGN_FEED_MAX_RANGES)]
+
+
 EXPORTS = {
     "mgn_abi_version": (_i32, []),
     "mgn_last_error": (ctypes.c_char_p, []),
@@ -158,6 +166,8 @@ EXPORTS = {
     "mgn_gmm_nll_diag": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _i64, _u32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mgn_gmm_nll_diag_backward": (_i32, [_vp, _vp, _i64, _i32, _i32, _f32, _vp, _i64, _u32, _vp, _vp, _vp, _vp]),
     "mgn_gmm_sample_diag": (_i32, [_vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
+    "mgn_feed_batch": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _i32, FeedRanges, _vp, _vp, _i64,
+                              _vp, _i64, _vp, _i64, _vp]),
     "mgn_adamw": (_i32, [_vp, _vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, _dbl, _dbl, _i64, _vp]),
     "mgn_adamw_dev": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _dbl, _dbl, _dbl, _dbl, _vp, _vp]),
     "mgn_adamw_dev2": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _dbl, _dbl, _dbl, _dbl, _vp, _i32, _vp]),
@@ -459,3 +469,42 @@ def normalizer_forward(x, accumulate, pending, acc_sum, acc_sum_sq, acc_count, n
                                        ptr(acc_sum_sq), ptr(acc_count), ptr(num_acc), float(max_acc),
                                        float(eps), ptr(out), ptr(ws), ws.numel(), stream_ptr(x.device)))
     return out
+
+
+def feed_ranges(ranges):
+    """mgn_feed_ranges of [(start, end), ...] (at most MGN_FEED_MAX_RANGES; the library checks the values)."""
+    ranges = list(ranges)
+    if len(ranges) > MGN_FEED_MAX_RANGES:
+        raise ValueError(f"at most {MGN_FEED_MAX_RANGES} noisy column ranges, got {len(ranges)}")
+    r = FeedRanges()
+    r.n = len(ranges)
+    for i, (s, e) in enumerate(ranges):
+        r.start[i], r.end[i] = int(s), int(e)
+    return r
+
+
+def feed_batch(traj, graph_ptr, frame, y_columns, type_index, ranges, scales, z, x, y):
+    """One training batch from resident trajectories (mgn_feed_batch): x[:, :F] = frame[g] of traj [T, N, F]
+    for the nodes of graph g, plus z * scales on the noisy column ranges of NORMAL rows; y = columns
+    y_columns of the next clean frame. graph_ptr / frame: int32 device tensors [B+1] / [B]; z None: no
+    noise. Writes x and y in place (x may be wider than F) on the current stream."""
+    import torch
+
+    require_device(traj)
+    if traj.dtype != torch.float32 or traj.dim() != 3 or not traj.is_contiguous():
+        raise ValueError("feed_batch: traj must be a contiguous fp32 [T, N, F] tensor")
+    T, N, F = traj.shape
+    for name, t, rows in (("x", x, N), ("y", y, N), ("z", z, N)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != rows or
+                              (t.shape[1] > 1 and t.stride(1) != 1) or t.device != traj.device):
+            raise ValueError(f"feed_batch: {name} must be an fp32 [{rows}, cols] tensor on traj's device with "
+                             "unit column stride")
+    if graph_ptr.dtype != torch.int32 or frame.dtype != torch.int32 or graph_ptr.numel() != frame.numel() + 1:
+        raise ValueError("feed_batch: graph_ptr [B+1] and frame [B] must be int32 tensors")
+    if x.shape[1] < F or y.shape[1] != y_columns[1] - y_columns[0]:
+        raise ValueError("feed_batch: x needs at least F columns and y exactly y_columns[1] - y_columns[0]")
+    rg = ranges if isinstance(ranges, FeedRanges) else feed_ranges(ranges)
+    check(lib().mgn_feed_batch(ptr(traj), T, N, F, ptr(graph_ptr), frame.numel(), ptr(frame), int(y_columns[0]),
+                               int(y_columns[1]), int(type_index), rg, ptr(scales), ptr(z),
+                               z.stride(0) if z is not None else 0, ptr(x), x.stride(0), ptr(y), y.stride(0),
+                               stream_ptr(traj.device)))

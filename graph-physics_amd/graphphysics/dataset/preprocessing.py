@@ -67,6 +67,10 @@ def add_world_pos_features(graph, world_pos_index_start: int, world_pos_index_en
 
 def add_noise(graph, noise_index_start: Union[int, List[int]], noise_index_end: Union[int, List[int]],
               noise_scale: Union[float, List[float]], node_type_index: int, t: Optional[float] = None):
+    """The reference's add_noise, its in-place write of graph.x included: on frames that are kept on the device
+    and reused (rather than re-read per item, as the reference's datasets do) the noise accumulates in the stored
+    data call after call — pass a copy, or train from dataset.resident.ResidentTrajectories, which never writes
+    the stored frames."""
     if isinstance(noise_index_start, int):
         noise_index_start = [noise_index_start]
     if isinstance(noise_index_end, int):

@@ -35,6 +35,13 @@ replays the tensors it recorded: assigning a new batch (`step.batch = b`) copies
 edge_attr into them when b shares the recorded edge_index (same tensor, unmodified); any other new
 batch is re-captured (a different topology).
 
+Resident trajectories (`feed=`, graphphysics.dataset.resident.ResidentTrajectories): feed.fill(batch) — the
+per-graph frame draw, the noise draw and ONE libmgn launch that writes the batch's x and y — is the first
+device work of every step: recorded at the head of the captured step (ahead of the recorded statistics
+exchange), run eagerly before the statistics exchange where that exchange is eager. Each replay then trains
+on a new batch and the host still only writes {lr, step}. Switching the feed between drawn and explicit
+frames re-records the step (the draw is, or is not, part of the graph).
+
 Validation errors flagged on libmgn's device error word (out-of-range edge_index, node types outside
 the one-hot range) surface as the reference's IndexError / RuntimeError at most one step late,
 without a host synchronisation per step. The device predicates the state updates on that word (ABI
@@ -77,8 +84,12 @@ def control_group(group=None):
 
 class TrainStep:
     def __init__(self, sim, opt, sched, batch, masks=(NodeType.NORMAL, NodeType.OUTFLOW), graph=True,
-                 group=None, data_parallel=None):
+                 group=None, data_parallel=None, feed=None):
         self.sim, self.opt, self.sched, self.batch = sim, opt, sched, batch
+        # feed (dataset.resident.ResidentTrajectories): its fill(batch) is the first device work of every
+        # step — recorded at the head of the captured step, so each replay trains on newly drawn frames and noise
+        self.feed = feed
+        self._feed_random = None  # the feed's frame mode the graph was recorded in
         self.masks = list(masks)
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
@@ -184,6 +195,8 @@ class TrainStep:
         try:
             nat.poll_errors(self.batch.x.device)
             self.opt.zero_grad(set_to_none=True)
+            if self.feed is not None:
+                self.feed.fill(self.batch)
             self._prologue()
             loss = self._loss()  # the Simulator / topology build poll the error word too
         except (IndexError, RuntimeError) as ex:
@@ -331,6 +344,11 @@ class TrainStep:
         # "global" capture mode would turn that query into hipErrorStreamCaptureUnsupported (abort)
         mode = "thread_local" if dist.is_available() and dist.is_initialized() else "global"
         with torch.cuda.graph(g, capture_error_mode=mode):
+            if self.feed is not None and (self.overlap or not self.dp):
+                # the batch itself is made inside the graph (frame and noise draws + one libmgn launch), ahead
+                # of the recorded statistics exchange: the statistics and the mask count see the fed batch
+                self.feed.fill(self.batch)
+                self._feed_random = self.feed.random_frames
             if self.overlap:
                 # RCCL: the statistics exchange (one statistics launch, the mask count, ONE all-reduce) is
                 # recorded too — it depends only on the batch the graph reads — so a step is ONE replay
@@ -378,6 +396,8 @@ class TrainStep:
             raise
         if self.graph is not None:
             self._sync_batch()
+            if self._feed_random is not None and self.feed.random_frames != self._feed_random:
+                self.graph = None  # the recorded fill draws (or does not draw) its frames: record it anew
         if self._ctl is not None:
             # re-capture on every rank if any rank needs to (a rank that copies and
             # replays while another re-captures would pair mismatched collectives)
@@ -394,6 +414,8 @@ class TrainStep:
         if self.dp and self.overlap:
             self.graph.replay()  # statistics exchange, backward-overlapped gradient all-reduce + AdamW inside
         elif self.dp:
+            if self.feed is not None:
+                self.feed.fill(self.batch)  # eager, as the statistics exchange that reads the fed batch
             self._prologue()
             self.graph.replay()
             if self._gflat is not None and dist.is_available() and dist.is_initialized():

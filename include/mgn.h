@@ -509,6 +509,40 @@ int mgn_gmm_sample_diag(const float* params, int64_t rows, int32_t d, int32_t K,
                         const float* u /* [rows] */, const float* z /* [rows, d] */, float* out /* [rows, d] */,
                         mgn_stream_t stream);
 
+/* Resident trajectories: a training batch's x and y from trajectories kept clean on the device, in one
+ * launch (the reference's Dataset.__getitem__ frame pick, dataset/h5_dataset.py:81-92, and its add_noise,
+ * dataset/preprocessing.py:177-238). traj [T, N, F] contiguous fp32: T frames of the N nodes of the batch's
+ * B graphs concatenated; graph g owns rows graph_ptr[g] .. graph_ptr[g+1] - 1 (graph_ptr[0] == 0,
+ * graph_ptr[B] == N, non-decreasing; empty graphs allowed). For a node r of graph g, with t = frame[g]:
+ *   x[r, c] = traj[t, r, c]                                   for every c < F
+ *   x[r, c] = traj[t, r, c] + z[r, zc] * scales[i]            c inside noisy range i and
+ *                                                             traj[t, r, type_index] == 0 (NodeType.NORMAL)
+ *   y[r, j] = traj[t + 1, r, y_start + j]                     always the clean next frame
+ * zc is the running column index over the ranges in the order given (range 0 owns z columns
+ * 0 .. end[0]-start[0]-1, and so on). The sum is torch's fp32 composition bit for bit: the rounded product,
+ * then the rounded add, never an FMA. z == NULL: no noise. traj is never written; columns of x at or
+ * beyond F (ldx > F) are left alone. scales and frame are read on the device at run time: the host may
+ * rewrite them between replays of a captured launch. frame[g] must lie in [0, T-2]: a precondition (the
+ * caller owns frame), not checked on the device. One launch, no atomics, no workspace; N == 0 or B == 0
+ * returns 0 without launching. Before any launch, a nonzero status for T < 2, F < 1, a range outside
+ * [0, F], overlapping ranges, a y range outside [0, F], type_index outside [0, F), n > 4, or an ld too
+ * small. The added symbol does not change MGN_ABI_VERSION; MGN_HAS_FEED marks headers that declare it. */
+#define MGN_HAS_FEED 1
+#define MGN_FEED_MAX_RANGES 4
+typedef struct mgn_feed_ranges {           /* passed by value at launch */
+    int32_t n;                             /* 0..MGN_FEED_MAX_RANGES noisy column ranges */
+    int32_t start[MGN_FEED_MAX_RANGES], end[MGN_FEED_MAX_RANGES];   /* columns of a frame row */
+} mgn_feed_ranges;
+int mgn_feed_batch(const float* traj, int64_t T, int64_t N, int32_t F,   /* [T, N, F] contiguous fp32 */
+                   const int32_t* graph_ptr, int32_t B,    /* device, [B+1] node offsets, graph_ptr[B] == N */
+                   const int32_t* frame,                   /* device, [B], 0 <= frame[g] <= T-2 */
+                   int32_t y_start, int32_t y_end,         /* y = traj[frame+1][:, y_start:y_end] */
+                   int32_t type_index,                     /* node-type column of a frame row */
+                   mgn_feed_ranges ranges,
+                   const float* scales,                    /* device, [ranges.n] (host may rewrite between replays) */
+                   const float* z, int64_t ldz,            /* device standard normals [N, Σ(end-start)]; NULL: no noise */
+                   float* x, int64_t ldx, float* y, int64_t ldy, mgn_stream_t stream);
+
 /* torch.optim.AdamW semantics (decoupled weight decay p *= 1 - lr*wd, bias-corrected moments,
  * denominator sqrt(v)/sqrt(1-beta2^t) + eps), fp32, over n contiguous elements. */
 int mgn_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
