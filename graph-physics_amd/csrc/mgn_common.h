@@ -121,6 +121,60 @@ __device__ __forceinline__ float type_mask_of(const float* nt, int64_t ld, int64
     return (v == (float)t && t >= 0 && t < 32 && ((tmask >> t) & 1u)) ? 1.f : 0.f;
 }
 
+// --------------------------------------------------------------------------- masked L2 sums
+// The arithmetic of mgn_masked_mse, shared with mgn_rollout_end so both compile the same expressions and
+// reduce in the same order (the rollout's per-step loss is masked_mse's value bit for bit): at most
+// MSE_BLOCKS blocks of 256 threads, block b owns rows [b·rpb, (b+1)·rpb), thread i of it rows r0 + i,
+// r0 + i + 256, ...; an LDS tree over the 256 threads; a single wave sums the blocks.
+constexpr int MSE_BLOCKS = 64;
+inline int64_t mse_rows_per_block(int64_t rows) {
+    const int64_t rpb = cdiv64(rows > 0 ? rows : 1, MSE_BLOCKS);
+    return rpb < 256 ? 256 : rpb;
+}
+inline int mse_blocks(int64_t rows) { return (int)cdiv64(rows > 0 ? rows : 1, mse_rows_per_block(rows)); }
+// e + (p - t)²: one column's term of a row's squared error
+__device__ __forceinline__ float mse_col_add(float e, float p, float t) {
+    const float d = p - t;
+    e += d * d;
+    return e;
+}
+// acc + m·e: a row's masked term
+__device__ __forceinline__ float mse_row_add(float acc, float m, float e) {
+    acc += m * e;
+    return acc;
+}
+// sum of K values per thread over the 256 threads of a block, pairwise in a fixed order; the sums end in
+// s[k][0]. s[k][threadIdx.x] must hold thread threadIdx.x's values (the call begins with a barrier).
+template <int K>
+__device__ __forceinline__ void mse_block_tree(float (*s)[256]) {
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) s[k][threadIdx.x] += s[k][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+}
+// one wave's sum of a value per lane (xor butterfly, every lane ends with the sum)
+__device__ __forceinline__ float mse_wave_sum(float v) {
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1) v += __shfl_xor(v, w);
+    return v;
+}
+
+// --------------------------------------------------------------------------- resident trajectories
+// The graph g of node r, graph_ptr[g] <= r < graph_ptr[g + 1], from the B + 1 node offsets (empty graphs
+// are stepped over; the same few cache lines for every thread).
+__device__ __forceinline__ int graph_of_row(const int32_t* __restrict__ graph_ptr, int B, int64_t r) {
+    int lo = 0, hi = B;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)graph_ptr[mid] <= r) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
 // --------------------------------------------------------------------------- packed weights
 // Forward fragments of W[n][k] (nn.Linear weight [out, in]):
 //   pack[((nt*KS + ks)*64 + lane)*VEC + v] = W[nt*16 + (lane&15)][ks*KSTEP + VEC*(lane>>4) + v]

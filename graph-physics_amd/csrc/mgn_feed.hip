@@ -34,13 +34,7 @@ __global__ __launch_bounds__(256) void feed_batch(const float* __restrict__ traj
     else
         r = e / F;
     const int c = (int)(e - r * F);
-    // the graph g with graph_ptr[g] <= r < graph_ptr[g + 1] (empty graphs are stepped over)
-    int lo = 0, hi = B;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((int64_t)graph_ptr[mid] <= r) lo = mid; else hi = mid;
-    }
-    const int64_t t = frame[lo];
+    const int64_t t = frame[graph_of_row(graph_ptr, B, r)];
     const float* src = traj + (t * N + r) * F;
     float v = src[c];
     if (z != nullptr) {

@@ -455,40 +455,30 @@ __global__ __launch_bounds__(256) void normalizer_apply(const float* __restrict_
 
 // Masked L2 loss (reference utils/loss.py:10-65 in its masked_mse form): one block, rows strided
 // over the threads, fixed-order tree: deterministic. Row mask: type_mask_of (mgn_common.h).
-// partial sums per block (fixed row range, strided threads, LDS tree) -> part[block] = {Σ m·err, Σ m}
-constexpr int MSE_BLOCKS = 64;
+// partial sums per block (fixed row range, strided threads, LDS tree) -> part[block] = {Σ m·err, Σ m}.
+// The row term, the tree and the wave sum are mgn_common.h's (shared with mgn_rollout_end).
 __global__ __launch_bounds__(256) void masked_mse_partial(const float* __restrict__ pred,
                                                           const float* __restrict__ tgt, int64_t rows, int cols,
                                                           const float* __restrict__ nt, int64_t nt_ld,
                                                           unsigned tmask, int64_t rows_per_block,
                                                           float* __restrict__ part) {
-    __shared__ float ra[256], rc[256];
+    __shared__ float red[2][256];
     const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
     const int64_t r1 = r0 + rows_per_block < rows ? r0 + rows_per_block : rows;
     float acc = 0.f, cnt = 0.f;
     for (int64_t r = r0 + threadIdx.x; r < r1; r += 256) {
         const float m = type_mask_of(nt, nt_ld, r, tmask);
         float e = 0.f;
-        for (int c = 0; c < cols; ++c) {
-            const float d = pred[r * cols + c] - tgt[r * cols + c];
-            e += d * d;
-        }
-        acc += m * e;
+        for (int c = 0; c < cols; ++c) e = mse_col_add(e, pred[r * cols + c], tgt[r * cols + c]);
+        acc = mse_row_add(acc, m, e);
         cnt += m;
     }
-    ra[threadIdx.x] = acc;
-    rc[threadIdx.x] = cnt;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            ra[threadIdx.x] += ra[threadIdx.x + w];
-            rc[threadIdx.x] += rc[threadIdx.x + w];
-        }
-        __syncthreads();
-    }
+    red[0][threadIdx.x] = acc;
+    red[1][threadIdx.x] = cnt;
+    mse_block_tree<2>(red);
     if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = ra[0];
-        part[2 * blockIdx.x + 1] = rc[0];
+        part[2 * blockIdx.x] = red[0][0];
+        part[2 * blockIdx.x + 1] = red[1][0];
     }
 }
 
@@ -500,11 +490,8 @@ __global__ __launch_bounds__(64) void masked_mse_final(const float* __restrict__
         a += part[2 * b];
         c += part[2 * b + 1];
     }
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) {
-        a += __shfl_xor(a, w);
-        c += __shfl_xor(c, w);
-    }
+    a = mse_wave_sum(a);
+    c = mse_wave_sum(c);
     if (lane == 0) {
         const float cc = count_dev ? *count_dev : c;
         *loss = a / (cc * (float)cols);
@@ -861,9 +848,8 @@ int mgn_masked_mse(const float* pred, const float* target, int64_t rows, int32_t
     MGN_REQUIRE(ws_bytes >= mgn_masked_mse_workspace_bytes(rows), "masked_mse: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     float* part = reinterpret_cast<float*>(ws);
-    int64_t rpb = cdiv64(rows > 0 ? rows : 1, MSE_BLOCKS);
-    if (rpb < 256) rpb = 256;
-    const int nb = (int)cdiv64(rows > 0 ? rows : 1, rpb);
+    const int64_t rpb = mse_rows_per_block(rows);
+    const int nb = mse_blocks(rows);
     hipLaunchKernelGGL(masked_mse_partial, dim3(nb), dim3(256), 0, st, pred, target, rows, (int)cols, node_type,
                        nt_ld, type_mask, rpb, part);
     MGN_LAUNCH_CHECK();

@@ -168,6 +168,11 @@ EXPORTS = {
     "mgn_gmm_sample_diag": (_i32, [_vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "mgn_feed_batch": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _i32, FeedRanges, _vp, _vp, _i64,
                               _vp, _i64, _vp, _i64, _vp]),
+    "mgn_rollout_begin": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
+                                 _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "mgn_rollout_end_workspace_bytes": (_sz, [_i64]),
+    "mgn_rollout_end": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _u32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                               _vp, _sz, _vp]),
     "mgn_adamw": (_i32, [_vp, _vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, _dbl, _dbl, _i64, _vp]),
     "mgn_adamw_dev": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _dbl, _dbl, _dbl, _dbl, _vp, _vp]),
     "mgn_adamw_dev2": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _dbl, _dbl, _dbl, _dbl, _vp, _i32, _vp]),
@@ -508,3 +513,91 @@ def feed_batch(traj, graph_ptr, frame, y_columns, type_index, ranges, scales, z,
                                int(y_columns[1]), int(type_index), rg, ptr(scales), ptr(z),
                                z.stride(0) if z is not None else 0, ptr(x), x.stride(0), ptr(y), y.stride(0),
                                stream_ptr(traj.device)))
+
+
+def _rollout_2d(fn, name, t, rows, dev, cols=None):
+    import torch
+
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != rows or t.device != dev or \
+            (t.shape[1] > 1 and t.stride(1) != 1) or (cols is not None and t.shape[1] != cols):
+        want = "cols" if cols is None else str(cols)
+        raise ValueError(f"{fn}: {name} must be an fp32 [{rows}, {want}] tensor on {dev} with unit column stride")
+
+
+def rollout_begin(traj, graph_ptr, frame, cursor, y_columns, out_columns, prev_columns, last, last_prev, x, y):
+    """Step s = cursor of a resident rollout, before the forward (mgn_rollout_begin): x[:, :F] = frame[g] + s of
+    traj [T, N, F] for the nodes of graph g, with `last` in out_columns and `last_prev` in prev_columns when
+    s > 0; y = y_columns of the next frame. prev_columns None (or empty): no previous data. cursor: int32 device
+    tensor of one element. Writes x and y in place (x may be wider than F) on the current stream."""
+    import torch
+
+    require_device(traj)
+    if traj.dtype != torch.float32 or traj.dim() != 3 or not traj.is_contiguous():
+        raise ValueError("rollout_begin: traj must be a contiguous fp32 [T, N, F] tensor")
+    T, N, F = traj.shape
+    (ys, ye), (os_, oe) = (int(v) for v in y_columns), (int(v) for v in out_columns)
+    ps, pe = (int(v) for v in prev_columns) if prev_columns is not None else (0, 0)
+    _rollout_2d("rollout_begin", "x", x, N, traj.device)
+    _rollout_2d("rollout_begin", "y", y, N, traj.device, ye - ys)
+    _rollout_2d("rollout_begin", "last", last, N, traj.device, oe - os_)
+    if pe > ps:
+        if last_prev is None:
+            raise ValueError("rollout_begin: previous-data columns without last_prev")
+        _rollout_2d("rollout_begin", "last_prev", last_prev, N, traj.device, pe - ps)
+    for name, t, n in (("graph_ptr", graph_ptr, frame.numel() + 1), ("frame", frame, frame.numel()),
+                       ("cursor", cursor, 1)):
+        if t.dtype != torch.int32 or t.numel() != n or t.device != traj.device or not t.is_contiguous():
+            raise ValueError(f"rollout_begin: {name} must be a contiguous int32 tensor of {n} elements on {traj.device}")
+    if x.shape[1] < F:
+        raise ValueError("rollout_begin: x needs at least F columns")
+    check(lib().mgn_rollout_begin(ptr(traj), T, N, F, ptr(graph_ptr), frame.numel(), ptr(frame), ptr(cursor), ys, ye,
+                                  os_, oe, ps, pe, ptr(last), last.stride(0), ptr(last_prev if pe > ps else None),
+                                  last_prev.stride(0) if pe > ps else 0, ptr(x), x.stride(0), ptr(y), y.stride(0),
+                                  stream_ptr(traj.device)))
+
+
+def rollout_end_workspace(N, device):
+    import torch
+
+    return torch.empty(int(lib().mgn_rollout_end_workspace_bytes(N)), dtype=torch.uint8, device=device)
+
+
+def rollout_end(out, y, x, type_index, masks, out_start, last, last_prev, preds, cursor, loss, sq, ws=None):
+    """Step s = cursor of a resident rollout, after the forward (mgn_rollout_end): pred = y where the node type
+    x[:, type_index] is neither NORMAL nor OUTFLOW, else out; last = pred, last_prev = pred - x[:, out columns]
+    (None: not kept), preds[s] = pred (None: not kept), loss[s] = masked_mse(y, pred, node type, masks),
+    sq[s] = Σ (pred - y)², cursor += 1. out, y, last, last_prev: contiguous fp32 [N, d]; preds [capacity, N, d];
+    loss, sq [capacity]. Everything in place on the current stream; ws: rollout_end_workspace(N, device) or None
+    (allocated here)."""
+    import torch
+
+    require_device(out)
+    dev = out.device
+    if out.dim() != 2:
+        raise ValueError("rollout_end: out must be an fp32 [N, d] tensor")
+    N, d = out.shape
+    for name, t in (("out", out), ("y", y), ("last", last), ("last_prev", last_prev)):
+        if t is not None:
+            _rollout_2d("rollout_end", name, t, N, dev, d)
+            if not t.is_contiguous():
+                raise ValueError(f"rollout_end: {name} must be contiguous")
+    _rollout_2d("rollout_end", "x", x, N, dev)
+    if loss.dtype != torch.float32 or sq.dtype != torch.float32 or loss.dim() != 1 or sq.shape != loss.shape or \
+            loss.device != dev or sq.device != dev or not loss.is_contiguous() or not sq.is_contiguous():
+        raise ValueError("rollout_end: loss and sq must be contiguous fp32 [capacity] tensors on out's device")
+    capacity = loss.numel()
+    if preds is not None and (preds.dtype != torch.float32 or tuple(preds.shape) != (capacity, N, d) or
+                              preds.device != dev or not preds.is_contiguous()):
+        raise ValueError(f"rollout_end: preds must be a contiguous fp32 [{capacity}, {N}, {d}] tensor on {dev}")
+    if cursor.dtype != torch.int32 or cursor.numel() != 1 or cursor.device != dev:
+        raise ValueError("rollout_end: cursor must be an int32 tensor of one element on out's device")
+    if any(not 0 <= int(m) < 32 for m in masks):
+        raise ValueError("rollout_end: loss mask node types must lie in [0, 32)")
+    tmask = 0
+    for m in masks:
+        tmask |= 1 << int(m)
+    if ws is None:
+        ws = rollout_end_workspace(N, dev)
+    check(lib().mgn_rollout_end(ptr(out), ptr(y), ptr(x), N, x.stride(0), int(type_index), tmask, int(out_start), d,
+                                ptr(last), ptr(last_prev), ptr(preds), capacity, ptr(cursor), ptr(loss), ptr(sq),
+                                ptr(ws), ws.numel(), stream_ptr(dev)))

@@ -13,6 +13,11 @@ never sees this); here the noise goes into the batch, never into `traj`.
 
 Not supported: `previous_data`, per-frame positions or edge_attr (Lagrangian datasets), and trajectories of
 unequal length in one batch. batch.edge_index / edge_attr are never touched.
+
+The validation rollout reads the same resident frames (training.rollout.Rollout.rollout_resident):
+rollout_begin_torch / rollout_end_torch state, as torch ops on any device, the two rules libmgn's
+mgn_rollout_begin / mgn_rollout_end run around the Simulator's evaluation forward; there previous data is
+supported, noise is not applied.
 """
 import math
 
@@ -75,6 +80,75 @@ def fill_torch(traj, graph_ptr, frame, y_columns, node_type_index, ranges, scale
             x[:, s:e] = torch.where(normal, feature + noise, feature)
             zc += e - s
     return x, y
+
+
+def check_rollout_columns(F, y_columns, out_columns, prev_columns, node_type_index):
+    """The host-side preconditions of a resident rollout (ValueError): the model's output columns, the target
+    columns and, when used, the previous-data columns have one width d; the output and previous-data ranges
+    lie inside [0, F), do not overlap, and do not contain the node-type column (the rollout writes them,
+    and reads the node type of the written row). Returns d."""
+    (ys, ye), (os_, oe) = (int(v) for v in y_columns), (int(v) for v in out_columns)
+    d = oe - os_
+    if d < 1 or not 0 <= os_ < oe <= F:
+        raise ValueError(f"output columns ({os_}, {oe}) must be a non-empty range inside [0, {F})")
+    if ye - ys != d:
+        raise ValueError(f"the feed's y_columns ({ys}, {ye}) and the output columns ({os_}, {oe}) differ in width")
+    k = int(node_type_index)
+    if os_ <= k < oe:
+        raise ValueError(f"node_type_index {k} lies inside the output columns ({os_}, {oe})")
+    if prev_columns is not None:
+        ps, pe = (int(v) for v in prev_columns)
+        if not 0 <= ps < pe <= F:
+            raise ValueError(f"previous-data columns ({ps}, {pe}) must be a non-empty range inside [0, {F})")
+        if pe - ps != d:
+            raise ValueError(f"previous-data columns ({ps}, {pe}) and the output columns ({os_}, {oe}) differ in width")
+        if ps < oe and os_ < pe:
+            raise ValueError(f"previous-data columns ({ps}, {pe}) overlap the output columns ({os_}, {oe})")
+        if ps <= k < pe:
+            raise ValueError(f"node_type_index {k} lies inside the previous-data columns ({ps}, {pe})")
+    return d
+
+
+def rollout_begin_torch(traj, graph_ptr, frame, cursor, y_columns, out_columns, prev_columns, last, last_prev, x, y):
+    """mgn_rollout_begin's rule as torch ops on any device, in place on x [N, >= F] and y [N, d]: with
+    s = cursor (a one-element int tensor or an int) x[:, :F] = frame[g] + s of traj for the nodes of graph g,
+    then, when s > 0, x[:, out_columns] = last and x[:, prev_columns] = last_prev (prev_columns None: no
+    previous data); y = y_columns of the following frame. traj is only read. The CPU path of
+    Rollout.rollout_resident, and what the kernel is tested and timed against."""
+    T, N, F = traj.shape
+    s = int(cursor)
+    rows = torch.arange(N, device=traj.device)
+    t = frame.to(traj.device, torch.int64)[_node_graph(graph_ptr, N, traj.device)] + s
+    x[:, :F] = traj[t, rows]
+    if s > 0:
+        x[:, out_columns[0]:out_columns[1]] = last
+        if prev_columns is not None and prev_columns[1] > prev_columns[0]:
+            x[:, prev_columns[0]:prev_columns[1]] = last_prev
+    y.copy_(traj[t + 1, rows, y_columns[0]:y_columns[1]])
+
+
+def rollout_end_torch(out, y, x, node_type_index, masks, out_start, last, last_prev, preds, cursor, loss, sq):
+    """mgn_rollout_end's rule as torch ops on any device, in place on its state: with s = cursor,
+    pred = y where the node type x[:, node_type_index] is neither NORMAL nor OUTFLOW (training.rollout.build_mask)
+    and out elsewhere; last_prev = pred - x[:, out columns] (None: not kept), last = pred, preds[s] = pred (None:
+    not kept), loss[s] = masked_mse(y, pred, node type, masks) — masked_mse itself —, sq[s] = Σ (pred - y)²,
+    cursor += 1 (cursor: a one-element int tensor). Returns pred."""
+    from graphphysics.utils.loss import masked_mse
+
+    s = int(cursor)
+    d = out.shape[1]
+    node_type = x[:, node_type_index]
+    keep = torch.logical_not(torch.logical_or(node_type == NodeType.NORMAL, node_type == NodeType.OUTFLOW))
+    pred = torch.where(keep[:, None], y, out)
+    if last_prev is not None:
+        last_prev.copy_(pred - x[:, out_start:out_start + d])
+    last.copy_(pred)
+    if preds is not None:
+        preds[s] = pred
+    loss[s] = masked_mse(y, pred, node_type, list(masks))
+    sq[s] = ((pred - y) ** 2).sum()
+    cursor += 1
+    return pred
 
 
 class ResidentTrajectories:

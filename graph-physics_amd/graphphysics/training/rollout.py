@@ -17,6 +17,12 @@ the previous prediction into the static input, Simulator eval forward, mask, kee
 is one hipGraph replay; the host only copies the next frame's x and y into the static buffers.
 Masking uses torch.where (the reference's boolean index_put would synchronise with the host). The
 graph is re-recorded when the mesh (edge_index) changes.
+
+With feed=ResidentTrajectories (dataset/resident.py), rollout_resident runs a whole trajectory from frames kept
+on the device as one replay per step of a single captured graph: libmgn's mgn_rollout_begin (frame start + s,
+the previous prediction fed back when s > 0), the same Simulator eval forward, mgn_rollout_end (mask, feedback
+state, the kept prediction, the step's loss and squared error, s += 1). The step counter s lives on the device;
+the host neither builds per-frame batches nor keeps lists of predictions, and never synchronises.
 """
 import math
 import weakref
@@ -42,9 +48,14 @@ class _Frame:
         self.__dict__.update(kw)
 
 
+class _Resident:
+    """The device state of rollout_resident for one mesh and shape: the static batch the graph reads, the
+    feedback state, the result buffers and the step counter."""
+
+
 class Rollout:
     def __init__(self, sim, node_type_index, masks=(NodeType.NORMAL, NodeType.OUTFLOW), use_previous_data=False,
-                 previous_data_start=None, previous_data_end=None, graph=True):
+                 previous_data_start=None, previous_data_end=None, graph=True, feed=None):
         self.sim = sim
         self.k = int(node_type_index)
         self.masks = list(masks)
@@ -55,6 +66,19 @@ class Rollout:
         self._graph = None
         self._key = None
         self.outputs, self.targets, self.losses = [], [], []
+        # feed (dataset.resident.ResidentTrajectories): the trajectories rollout_resident reads. A validation
+        # feed of its own: set_frames puts it into explicit mode, a TrainStep sharing it would re-record.
+        self.feed = feed
+        self._res = None  # rollout_resident's state (_Resident)
+        self.resident_records = 0  # how many times rollout_resident recorded its graph
+        self._res_sq, self._res_count = [], 0  # Σ (pred − target)² per resident run (device), and their elements
+        if feed is not None:
+            from graphphysics.dataset.resident import check_rollout_columns
+
+            if torch.device(sim.device).type != feed.traj.device.type:
+                raise ValueError(f"feed lives on {feed.traj.device}, the simulator on {sim.device}")
+            self._prev_cols = (int(self.ps), int(self.pe)) if self.use_prev else None
+            check_rollout_columns(feed.F, feed.y_columns, (self.os, self.oe), self._prev_cols, self.k)
         self.reset()
 
     # ------------------------------------------------------------------ trajectory bookkeeping
@@ -68,6 +92,7 @@ class Rollout:
         self.outputs.clear()
         self.targets.clear()
         self.losses.clear()
+        self._res_sq, self._res_count = [], 0
         self.reset()
 
     # ------------------------------------------------------------------ one step
@@ -160,7 +185,150 @@ class Rollout:
         self.reset()
         return torch.stack([self.step(b)[0] for b in frames])
 
+    # ------------------------------------------------------------------ resident trajectories
+    def _resident_same(self, batch, keep):
+        """As _same_mesh: the state (and its recorded graph) holds the topology of this exact edge_index tensor
+        and buffers of these shapes; keeping the predictions or not is part of what was recorded."""
+        if self._res is None:
+            return False
+        ref, ver, xs, ys, ea, kept = self._res.key
+        return (ref() is batch.edge_index and ver == batch.edge_index._version and xs == batch.x.shape
+                and ys == batch.y.shape and ea == (None if batch.edge_attr is None else batch.edge_attr.shape)
+                and kept == keep)
+
+    def _resident_alloc(self, batch, keep):
+        feed, dev = self.feed, batch.x.device
+        d, cap = self.oe - self.os, self.feed.T - 1  # a trajectory of T frames has at most T − 1 steps
+        st = _Resident()
+        st.x, st.y = batch.x.clone(), batch.y.clone()
+        st.edge_attr = batch.edge_attr.clone() if batch.edge_attr is not None else None  # transformer models: none
+        st.frame = _Frame(x=st.x, y=st.y, edge_index=batch.edge_index, edge_attr=st.edge_attr,
+                          pos=getattr(batch, "pos", None))
+        st.last = torch.zeros(feed.N, d, dtype=torch.float32, device=dev)
+        st.last_prev = torch.zeros_like(st.last) if self.use_prev else None
+        st.preds = torch.zeros(cap, feed.N, d, dtype=torch.float32, device=dev) if keep else None
+        st.loss = torch.zeros(cap, dtype=torch.float32, device=dev)
+        st.sq = torch.zeros(cap, dtype=torch.float32, device=dev)
+        st.cursor = torch.zeros(1, dtype=torch.int32, device=dev)  # the step counter: only the end stage writes it
+        st.ws, st.graph, st.topo = None, None, None
+        if dev.type == "cuda":
+            from graphphysics import _native as nat
+
+            st.ws = nat.rollout_end_workspace(feed.N, dev)
+        st.key = (weakref.ref(batch.edge_index), batch.edge_index._version, batch.x.shape, batch.y.shape,
+                  None if batch.edge_attr is None else batch.edge_attr.shape, keep)
+        return st
+
+    def _resident_step(self, st):
+        """Step `cursor`: frame and feedback into the static batch, the evaluation forward, mask / state /
+        results. Three stages of device work and nothing else, so it records as it runs."""
+        feed = self.feed
+        if st.x.is_cuda:
+            from graphphysics import _native as nat
+
+            begin, end, extra = nat.rollout_begin, nat.rollout_end, (st.ws,)
+        else:
+            from graphphysics.dataset.resident import rollout_begin_torch as begin, rollout_end_torch as end
+
+            extra = ()
+        begin(feed.traj, feed.graph_ptr, feed.frame, st.cursor, feed.y_columns, (self.os, self.oe), self._prev_cols,
+              st.last, st.last_prev, st.x, st.y)
+        with torch.no_grad():
+            _, _, out = self.sim(st.frame)
+        end(out, st.y, st.x, self.k, self.masks, self.os, st.last, st.last_prev, st.preds, st.cursor, st.loss, st.sq,
+            *extra)
+
+    def _resident_record(self, st):
+        dev = st.x.device
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):  # warm-up: topology cache, weight packs, allocator
+            st.cursor.zero_()
+            self._resident_step(st)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        # the graph reads this topology's buffers: keep them alive beyond the topology cache
+        from graphphysics.models import _engine
+
+        st.topo = _engine.get_topology(st.frame.edge_index, st.x.size(0))
+        g = torch.cuda.CUDAGraph()
+        import torch.distributed as dist
+
+        mode = "thread_local" if dist.is_available() and dist.is_initialized() else "global"  # see _record
+        with torch.cuda.graph(g, capture_error_mode=mode):
+            self._resident_step(st)
+        st.graph = g
+        self.resident_records += 1
+
+    def rollout_resident(self, batch, start=0, steps=None, keep_predictions=True):
+        """One whole trajectory from the feed's resident frames: step s reads frame start[g] + s of graph g,
+        feeds the previous prediction back from step 1 on, and compares with frame start[g] + s + 1 — _predict
+        and step over `steps` frames, with the step counter, the feedback state and the results on the device.
+        With graph=True (HIP tensors) every step is one replay of one captured graph, recorded on the first call
+        and again only when the mesh (edge_index) or the shapes change; otherwise, and on CPU tensors (torch
+        forms), the same three stages run eagerly per step.
+
+        batch: the static x [N, >= F], y [N, d], edge_index, edge_attr (None for transformer models) and pos;
+        cloned like TrainStep's (x's columns beyond F and edge_attr are re-read on every call). start: an int
+        or one int per graph; steps: default T − 1 − max(start). Returns the predictions [steps, N, d] (None
+        with keep_predictions=False); extends self.losses by the per-step losses (0-dim device tensors) and
+        adds to what all_rollout_rmse() reports. Nothing here synchronises with the host."""
+        feed = self.feed
+        if feed is None:
+            raise ValueError("rollout_resident needs Rollout(..., feed=ResidentTrajectories)")
+        if self.sim.training:
+            raise RuntimeError("rollout_resident runs the evaluation forward: call sim.eval() first")
+        x, y, d = batch.x, batch.y, self.oe - self.os
+        if x.device != feed.traj.device or x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != feed.N or \
+                x.shape[1] < feed.F or self.k >= x.shape[1]:
+            raise ValueError(f"batch.x must be fp32 [{feed.N}, >= {max(feed.F, self.k + 1)}] on {feed.traj.device}, "
+                             f"got {tuple(x.shape)} {x.dtype} on {x.device}")
+        if y is None or y.device != x.device or y.dtype != torch.float32 or tuple(y.shape) != (feed.N, d):
+            raise ValueError(f"batch.y must be fp32 [{feed.N}, {d}] on {feed.traj.device}")
+        if torch.is_tensor(start):
+            start = start.tolist()
+        starts = [int(s) for s in start] if isinstance(start, (list, tuple)) else [int(start)] * feed.B
+        if len(starts) != feed.B:
+            raise ValueError(f"expected one start frame per graph ({feed.B}), got {len(starts)}")
+        steps = feed.T - 1 - max(starts) if steps is None else int(steps)
+        if steps < 1 or max(starts) + steps > feed.T - 1:
+            raise ValueError(f"start {starts} and {steps} steps leave the trajectory: step s reads frames "
+                             f"start + s and start + s + 1 of {feed.T}")
+        feed.set_frames(starts)  # the host check of every start frame; the feed is in explicit mode from here
+        keep = bool(keep_predictions)
+        if self._resident_same(batch, keep):
+            st = self._res
+            st.x.copy_(x)
+            if st.edge_attr is not None:
+                st.edge_attr.copy_(batch.edge_attr)
+        else:
+            st = self._res = self._resident_alloc(batch, keep)
+        if steps > st.loss.numel():
+            raise ValueError(f"{steps} steps exceed the result buffers' capacity {st.loss.numel()}")
+        captured = self.use_graph and x.is_cuda
+        if captured and st.graph is None:
+            self._resident_record(st)
+        st.cursor.zero_()  # every call is a new trajectory; `last` is not read at step 0
+        for _ in range(steps):
+            if captured:
+                st.graph.replay()
+            else:
+                self._resident_step(st)
+        loss, sq = st.loss[:steps].clone(), st.sq[:steps].clone()
+        self.losses.extend(loss.unbind(0))
+        self._res_sq.append(sq)
+        self._res_count += steps * feed.N * d
+        return st.preds[:steps].clone() if keep else None
+
     def all_rollout_rmse(self):
-        p = torch.cat([o.float() for o in self.outputs])
-        t = torch.cat([o.float() for o in self.targets])
-        return math.sqrt(((p - t) ** 2).mean().item())
+        if not self._res_sq:
+            p = torch.cat([o.float() for o in self.outputs])
+            t = torch.cat([o.float() for o in self.targets])
+            return math.sqrt(((p - t) ** 2).mean().item())
+        # resident runs keep Σ (pred − target)² per step on the device: add them, in fp64 on the host, to what
+        # the lists hold
+        total, count = float(torch.cat(self._res_sq).cpu().double().sum()), self._res_count
+        for o, t in zip(self.outputs, self.targets):
+            total += float(((o.float() - t.float()) ** 2).sum().double())
+            count += o.numel()
+        return math.sqrt(total / count)

@@ -543,6 +543,48 @@ int mgn_feed_batch(const float* traj, int64_t T, int64_t N, int32_t F,   /* [T, 
                    const float* z, int64_t ldz,            /* device standard normals [N, Σ(end-start)]; NULL: no noise */
                    float* x, int64_t ldx, float* y, int64_t ldy, mgn_stream_t stream);
 
+/* Resident rollout: the data work of one autoregressive validation step (reference lightning_module.py:17-25,
+ * 168-249) around the Simulator's evaluation forward, driven by a step counter on the device (*cursor, int32),
+ * so a trajectory is S replays of one captured begin -> forward -> end. traj, graph_ptr and frame as in
+ * mgn_feed_batch; no noise. With s = *cursor and t = frame[g] + s for a node r of graph g:
+ *   mgn_rollout_begin   x[r, c] = traj[t, r, c] for every c < F, except, when s > 0,
+ *                         x[r, out_start + j]  = last[r, j]         (the previous step's prediction)
+ *                         x[r, prev_start + j] = last_prev[r, j]    (prev_start < prev_end: previous data)
+ *                       y[r, j] = traj[t + 1, r, y_start + j]. traj is never written; columns of x at or beyond
+ *                       F are left alone. One launch.
+ *   mgn_rollout_end     keep = x[r, type_index] is neither 0 (NORMAL) nor 5 (OUTFLOW)   (build_mask)
+ *                       pred[r, j] = keep ? y[r, j] : out[r, j]          out: the forward's outputs [N, d]
+ *                       last = pred; last_prev = pred - x[r, out_start + j] (when non-null);
+ *                       preds[s] = pred (when non-null, preds [capacity, N, d]);
+ *                       loss[s] = mgn_masked_mse(pred, y, node type x[:, type_index], loss_type_mask), bit for
+ *                       bit: the same blocks, rows per block, trees and final wave over the same row term;
+ *                       sq[s] = Σ_r Σ_j (pred - y)²; then *cursor = s + 1. Two launches (per-block partial sums
+ *                       {Σ m·err, Σ m, Σ err} into the workspace, a single-wave final pass in a fixed order),
+ *                       no atomics: bit-reproducible. Only the final pass writes *cursor.
+ * out, y (of _end), last, last_prev: row-major [N, d] without padding. frame[g] + *cursor in [0, T-2] and
+ * *cursor in [0, capacity) are the caller's to keep (it writes frame and knows how many steps it enqueued);
+ * outside them nothing is loaded or stored out of bounds: _begin skips the row, _end the whole step, and the
+ * counter stops. No allocation, no synchronisation: capturable. N == 0 (or B == 0) returns 0 without a launch.
+ * Before any launch, a nonzero status for T < 2, F < 1, a column range outside [0, F] (x's row for _end), an
+ * empty output range, overlapping output and previous-data ranges, type_index inside the output columns, an ld
+ * too small, capacity < 1 or a workspace too small. The added symbols do not change MGN_ABI_VERSION;
+ * MGN_HAS_ROLLOUT marks headers that declare them. */
+#define MGN_HAS_ROLLOUT 1
+int mgn_rollout_begin(const float* traj, int64_t T, int64_t N, int32_t F,   /* [T, N, F] contiguous fp32 */
+                      const int32_t* graph_ptr, int32_t B,    /* device, [B+1] node offsets, graph_ptr[B] == N */
+                      const int32_t* frame,                   /* device, [B]: the trajectory's first frame per graph */
+                      const int32_t* cursor,                  /* device, the step counter s */
+                      int32_t y_start, int32_t y_end,         /* y = traj[frame+s+1][:, y_start:y_end] */
+                      int32_t out_start, int32_t out_end,     /* columns of x the model predicts */
+                      int32_t prev_start, int32_t prev_end,   /* previous-data columns; equal: none */
+                      const float* last, int64_t ld_last, const float* last_prev, int64_t ld_prev,
+                      float* x, int64_t ldx, float* y, int64_t ldy, mgn_stream_t stream);
+size_t mgn_rollout_end_workspace_bytes(int64_t N);
+int mgn_rollout_end(const float* out, const float* y, const float* x, int64_t N, int64_t ldx, int32_t type_index,
+                    uint32_t loss_type_mask, int32_t out_start, int32_t d, float* last, float* last_prev,
+                    float* preds, int32_t capacity, int32_t* cursor, float* loss, float* sq, void* ws,
+                    size_t ws_bytes, mgn_stream_t stream);
+
 /* torch.optim.AdamW semantics (decoupled weight decay p *= 1 - lr*wd, bias-corrected moments,
  * denominator sqrt(v)/sqrt(1-beta2^t) + eps), fp32, over n contiguous elements. */
 int mgn_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
