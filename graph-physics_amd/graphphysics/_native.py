@@ -79,6 +79,13 @@ class FeedRanges(ctypes.Structure):
     _fields_ = [("n", _i32), ("start", _i32 * MGN_FEED_MAX_RANGES), ("end", _i32 * MGN_FEED_MAX_RANGES)]
 
 
+class GatedMlp(ctypes.Structure):
+    """mgn_gated_mlp: the fp32 master parameters of a Transformer block's norm2 + gated_mlp (mgn.h)."""
+    _fields_ = [("hidden", _i32), ("expand", _i32), ("dtype", _i32), ("norm_dim", _i32), ("max_blocks", _i32),
+                ("reserved", _i32), ("w1", _vp), ("b1", _vp),
+                ("w2", _vp), ("b2", _vp), ("w3", _vp), ("b3", _vp), ("scale_a", _vp), ("scale_b", _vp)]
+
+
 EXPORTS = {
     "mgn_abi_version": (_i32, []),
     "mgn_last_error": (ctypes.c_char_p, []),
@@ -145,6 +152,13 @@ EXPORTS = {
                                            _vp, _vp]),
     "mgn_graph_attention_backward": (_i32, [ctypes.POINTER(Topology), _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32,
                                             _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mgn_gated_mlp_row_tile": (_i32, []),
+    "mgn_gated_mlp_blocks": (_i32, [_i64, _i32]),
+    "mgn_gated_mlp_saved_bytes": (_sz, [ctypes.POINTER(GatedMlp), _i64]),
+    "mgn_gated_mlp_forward": (_i32, [ctypes.POINTER(GatedMlp), _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "mgn_gated_mlp_backward_workspace_bytes": (_sz, [ctypes.POINTER(GatedMlp), _i64]),
+    "mgn_gated_mlp_backward": (_i32, [ctypes.POINTER(GatedMlp), _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _sz,
+                                      _vp]),
     "mgn_permute_rows": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
     "mgn_segment_sum": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp]),
     "mgn_column_stats_workspace_bytes": (_sz, [_i64, _i32]),
@@ -601,3 +615,21 @@ def rollout_end(out, y, x, type_index, masks, out_start, last, last_prev, preds,
     check(lib().mgn_rollout_end(ptr(out), ptr(y), ptr(x), N, x.stride(0), int(type_index), tmask, int(out_start), d,
                                 ptr(last), ptr(last_prev), ptr(preds), capacity, ptr(cursor), ptr(loss), ptr(sq),
                                 ptr(ws), ws.numel(), stream_ptr(dev)))
+
+
+def gated_mlp_row_tile():
+    """Rows of one workgroup tile of the gated-MLP kernels (mgn_gated_mlp_row_tile)."""
+    return int(lib().mgn_gated_mlp_row_tile())
+
+
+def gated_mlp_blocks(rows, max_blocks=0):
+    """Workgroups of the gated-MLP row-tile kernels for `rows` rows: min(tiles, a fixed cap, max_blocks when
+    > 0); workgroup b takes the tiles b, b + blocks, ... (mgn_gated_mlp_blocks)."""
+    return int(lib().mgn_gated_mlp_blocks(int(rows), int(max_blocks)))
+
+
+def gated_mlp_desc(hidden, dtype, w1, b1, w2, b2, w3, b3, scale_a, scale_b, max_blocks=0):
+    """mgn_gated_mlp over the fp32 master parameters (tensors, raw addresses or None); max_blocks > 0 caps the
+    row-tile kernels' grid."""
+    return GatedMlp(int(hidden), 3 * int(hidden), int(dtype), int(hidden), int(max_blocks), 0, ptr(w1), ptr(b1), ptr(w2), ptr(b2),
+                    ptr(w3), ptr(b3), ptr(scale_a), ptr(scale_b))

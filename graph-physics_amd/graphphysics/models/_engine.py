@@ -990,6 +990,91 @@ class GraphAttentionFunction(torch.autograd.Function):
         return None, None, d[0].to(ctx.in_dtype), d[1].to(ctx.in_dtype), d[2].to(ctx.in_dtype)
 
 
+# --------------------------------------------------------------------------- gated MLP
+class GatedMLPFunction(torch.autograd.Function):
+    """y = x + gated_mlp(norm2(x)) of a Transformer block on libmgn (mgn_gated_mlp_forward / _backward, mgn.h):
+    x [N, h] (read as fp32, unit column stride), the eight parameters in module order (norm2.scale,
+    gated_mlp.0.scale, linear1.weight, .bias, linear2.weight, .bias, gated_mlp.2.weight, .bias) as fp32
+    masters — the kernels read them when they run, so a replayed graph sees what the optimizer wrote.
+    grad_mode: torch.is_grad_enabled() at the call, as EPDFunction; without it (or without an input that
+    needs a gradient) the inference forward runs and nothing is saved. The backward recomputes u and v from
+    x and the parameters as they are THEN: both go through save_for_backward, so autograd's version check
+    refuses a backward after an in-place change of either, and a retained graph can be run again. y, the
+    saved norms, the workspace and the flat gradient come from the caching allocator; nothing synchronises
+    with the host."""
+
+    @staticmethod
+    def _operands(x, params):
+        """(x, parameters) as the kernels read them: fp32, unit column stride / contiguous (no copy when
+        they already are)."""
+        xs = x.detach()
+        if xs.dtype != torch.float32 or (xs.shape[1] > 1 and xs.stride(1) != 1) or \
+                (xs.shape[0] > 1 and xs.stride(0) < xs.shape[1]):
+            xs = xs.float().contiguous()
+        ps = [p.detach() for p in params]
+        return xs, [p if p.dtype == torch.float32 and p.is_contiguous() else p.float().contiguous() for p in ps]
+
+    @staticmethod
+    def forward(ctx, mdt, grad_mode, x, *params):
+        nat.require_device(x)
+        if x.dim() != 2 or len(params) != 8:
+            raise ValueError("gated MLP: x must be [N, h] with the eight parameters of norm2 and gated_mlp")
+        xs, ps = GatedMLPFunction._operands(x, params)
+        N, h = xs.shape
+        dev = xs.device
+        shapes = [(h,), (h,), (3 * h, h), (3 * h,), (3 * h, h), (3 * h,), (h, 3 * h), (h,)]
+        if [tuple(p.shape) for p in ps] != shapes:
+            raise ValueError(f"gated MLP: parameter shapes {[tuple(p.shape) for p in ps]} do not fit hidden size {h}")
+        sa, sb, w1, b1, w2, b2, w3, b3 = ps
+        desc = nat.gated_mlp_desc(h, mdt, w1, b1, w2, b2, w3, b3, sa, sb)
+        train = grad_mode and any(ctx.needs_input_grad)
+        L = nat.lib()
+        y = torch.empty((N, h), dtype=torch.float32, device=dev)
+        saved = _empty(max(int(L.mgn_gated_mlp_saved_bytes(ctypes.byref(desc), N)), 4), torch.uint8, dev) \
+            if train else None
+        nat.check(L.mgn_gated_mlp_forward(ctypes.byref(desc), nat.ptr(xs), GatedMLPFunction._ld(xs), N, nat.ptr(y), h,
+                                          nat.ptr(saved), nat.stream_ptr(dev)))
+        if train:
+            ctx.mdt = mdt
+            ctx.save_for_backward(x, *params, saved)
+        return y if x.dtype == torch.float32 else y.to(x.dtype)
+
+    @staticmethod
+    def _ld(t):
+        return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+    @staticmethod
+    def backward(ctx, gy):
+        *inputs, saved = ctx.saved_tensors
+        x, params = inputs[0], inputs[1:]
+        xs, ps = GatedMLPFunction._operands(x, params)
+        sa, sb, w1, b1, w2, b2, w3, b3 = ps
+        N, h = xs.shape
+        dev = xs.device
+        desc = nat.gated_mlp_desc(h, ctx.mdt, w1, b1, w2, b2, w3, b3, sa, sb)
+        dy = gy.detach()
+        if dy.dtype != torch.float32 or (h > 1 and dy.stride(1) != 1) or (N > 1 and dy.stride(0) < h):
+            dy = dy.float().contiguous()
+        L = nat.lib()
+        wsb = int(L.mgn_gated_mlp_backward_workspace_bytes(ctypes.byref(desc), N))
+        ws = _empty(max(wsb, 4), torch.uint8, dev)
+        dx = torch.empty((N, h), dtype=torch.float32, device=dev)
+        G = torch.empty(sum(p.numel() for p in ps), dtype=torch.float32, device=dev)
+        if N == 0:
+            G.zero_()
+        nat.check(L.mgn_gated_mlp_backward(ctypes.byref(desc), nat.ptr(xs), GatedMLPFunction._ld(xs), N, nat.ptr(saved),
+                                           nat.ptr(dy), GatedMLPFunction._ld(dy), nat.ptr(dx), nat.ptr(G), nat.ptr(ws),
+                                           wsb, nat.stream_ptr(dev)))
+        out, o = [], 0
+        for i, p in enumerate(ps):
+            g = G[o:o + p.numel()].view(p.shape)
+            o += p.numel()
+            out.append((g if params[i].dtype == torch.float32 else g.to(params[i].dtype))
+                       if ctx.needs_input_grad[3 + i] else None)
+        gx = (dx if x.dtype == torch.float32 else dx.to(x.dtype)) if ctx.needs_input_grad[2] else None
+        return (None, None, gx, *out)
+
+
 class FlatGradFunction(torch.autograd.Function):
     """Identity on a module's parameters whose backward gathers their gradients into ONE flat fp32
     buffer laid out like module.parameters() and hands back views of it — what EPDFunction's backward

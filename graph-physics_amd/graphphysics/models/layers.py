@@ -6,8 +6,9 @@ scaled_dot_product_attention / Attention / Transformer 395-627, GraphNetBlock 63
 reference checkpoints load unchanged. GraphNetBlock.forward runs on libmgn (HIP, gfx950); there
 is no CPU fallback. The transformer family's attention core (the reference's DGL sparse branch) runs
 on libmgn's graph-attention kernels on a HIP tensor and as a torch composition
-(sparse_attention_torch) on a CPU tensor; its dense pieces (projections, gated MLP, stand-alone
-RMSNorm) are torch ops. DiagonalGMMHead (157-195) is the mixture-density decoder of
+(sparse_attention_torch) on a CPU tensor. The block's dense half, x + gated_mlp(norm2(x)), runs on libmgn's fused gated-MLP kernels
+(mgn_gated_mlp_*) when the block is built with dense="libmgn" (opt-in; the default "torch" is a composition
+of torch ops); the attention-side projections (norm1, q/k/v, proj) are torch ops. DiagonalGMMHead (157-195) is the mixture-density decoder of
 EncodeTransformDecode: two Linears (torch ops); its loss and sampler run on libmgn (utils/loss.py
 masked_gmm_nll, models/simulator.py sample_gmm_diagonal). The full-covariance GMMHead is out of scope.
 """
@@ -237,6 +238,13 @@ class Normalizer(nn.Module):
 # --------------------------------------------------------------------------- transformer family
 ATTENTION_HEADS = (1, 2, 4, 8)  # mgn_graph_attention_* (include/mgn.h)
 ATTENTION_MAX_HIDDEN = 256
+DENSE_MODES = ("torch", "libmgn")  # who runs x + gated_mlp(norm2(x)) of a Transformer block
+
+
+def check_dense(dense):
+    if dense not in DENSE_MODES:
+        raise ValueError(f"dense={dense!r}: must be one of {DENSE_MODES}")
+    return dense
 
 
 class GatedMLP(nn.Module):
@@ -390,12 +398,17 @@ class Attention(nn.Module):
 class Transformer(nn.Module):
     """x = x + attention(norm1(x), adj); x = x + gated_mlp(norm2(x)) (reference layers.py:548-627; the
     gated MLP starts with an RMSNorm of its own, so its input is normalised twice; `activation` is
-    constructed and never used, as in the reference). adj: an edge_index [2, E] tensor."""
+    constructed and never used, as in the reference). adj: an edge_index [2, E] tensor.
+
+    dense (keyword / set_dense): "torch" (default) — the second line is a composition of torch ops;
+    "libmgn" — on a HIP tensor it is one _engine.GatedMLPFunction (the fused gated-MLP kernels, in the
+    module's compute_dtype, no fallback), on a CPU tensor the torch composition, as the attention."""
 
     def __init__(self, input_dim: int, output_dim: int, num_heads: int, activation_layer: torch.nn.Module = nn.ReLU,
                  use_proj_bias: bool = True, use_separate_proj_weight: bool = True,
-                 compute_dtype: torch.dtype = None):
+                 compute_dtype: torch.dtype = None, dense: str = "torch"):
         super().__init__()
+        self.dense = check_dense(dense)
         self.compute_dtype = compute_dtype or default_compute_dtype()
         self.attention = Attention(input_dim=input_dim, output_dim=output_dim, num_heads=num_heads,
                                    use_proj_bias=use_proj_bias, use_separate_proj_weight=use_separate_proj_weight,
@@ -409,6 +422,17 @@ class Transformer(nn.Module):
         self.compute_dtype = self.attention.compute_dtype = dtype
         return self
 
+    def set_dense(self, dense):
+        self.dense = check_dense(dense)
+        return self
+
+    def _dense_half(self, x):
+        """x + gated_mlp(norm2(x)) on libmgn: one autograd node over the fp32 master parameters."""
+        g = self.gated_mlp
+        return _engine.GatedMLPFunction.apply(
+            nat.mgn_dtype(self.compute_dtype), torch.is_grad_enabled(), x, self.norm2.scale, g[0].scale,
+            g[1].linear1.weight, g[1].linear1.bias, g[1].linear2.weight, g[1].linear2.bias, g[2].weight, g[2].bias)
+
     def forward(self, x: torch.Tensor, adj, return_attention: bool = False):
         attn = None
         with _autocast(self.compute_dtype, x):
@@ -417,7 +441,10 @@ class Transformer(nn.Module):
                 x = x + x_
             else:
                 x = x + self.attention(self.norm1(x), adj, return_attention)
-            x = x + self.gated_mlp(self.norm2(x))
+            if self.dense == "libmgn" and x.is_cuda:
+                x = self._dense_half(x)
+            else:
+                x = x + self.gated_mlp(self.norm2(x))
         return (x, attn) if return_attention else x
 
 

@@ -14,7 +14,9 @@ torch.bfloat16 (bf16 storage, fp32 accumulation); also settable via GRAPHPHYSICS
 
 EncodeTransformDecode (configs with "type": "transformer") is the reference's DGL branch: nodes_encoder,
 Transformer blocks whose attention is masked by the mesh adjacency, decode_module; it reads no
-edge_attr. The attention core runs on libmgn's graph-attention kernels; the dense layers are torch ops.
+edge_attr. The attention core runs on libmgn's graph-attention kernels; with dense="libmgn" (opt-in) the
+dense half of every block, x + gated_mlp(norm2(x)), runs on libmgn's fused gated-MLP kernels. The
+attention-side projections, the encoder and the decoder are torch ops.
 """
 import torch
 import torch.nn as nn
@@ -22,7 +24,7 @@ import torch.nn as nn
 from graphphysics import _native as nat
 from graphphysics.models import _engine
 from graphphysics.models.layers import (ATTENTION_HEADS, ATTENTION_MAX_HIDDEN, DiagonalGMMHead, GraphNetBlock,
-                                        Transformer, _autocast, build_mlp, default_compute_dtype)
+                                        Transformer, _autocast, build_mlp, check_dense, default_compute_dtype)
 
 
 class EncodeProcessDecode(nn.Module):
@@ -97,6 +99,9 @@ class EncodeTransformDecode(nn.Module):
     Linear layers run as under torch.autocast(bfloat16), q, k, v, y and their gradients are bf16 for the
     kernels, norms, residuals and softmax are fp32, master weights and gradients fp32.
 
+    dense (keyword / set_dense): "torch" (default) or "libmgn" — who runs x + gated_mlp(norm2(x)) of every
+    block (layers.Transformer); parameters, state_dict keys and the flat buffer are the same either way.
+
     num_mixture_components = K > 0 (with use_diagonal=True and a temperature): decode_module is a
     DiagonalGMMHead and forward returns the mixture parameters [N, K(2·output_size+1)] in fp32 (its two
     Linears under the same autocast as the rest); train it with utils.loss.masked_gmm_nll, sample it with
@@ -108,8 +113,10 @@ class EncodeTransformDecode(nn.Module):
     def __init__(self, message_passing_num: int, node_input_size: int, output_size: int, hidden_size: int = 128,
                  num_heads: int = 4, only_processor: bool = False, use_proj_bias: bool = True,
                  use_separate_proj_weight: bool = True, num_mixture_components: int = 0,
-                 temperature: float = None, use_diagonal: bool = True, compute_dtype: torch.dtype = None):
+                 temperature: float = None, use_diagonal: bool = True, compute_dtype: torch.dtype = None,
+                 dense: str = "torch"):
         super().__init__()
+        self.dense = check_dense(dense)
         if num_mixture_components < 0:
             raise ValueError(f"num_mixture_components={num_mixture_components} must be >= 0")
         if num_mixture_components > 0 and temperature is None:
@@ -141,7 +148,8 @@ class EncodeTransformDecode(nn.Module):
         self.processor_list = nn.ModuleList(
             [Transformer(input_dim=hidden_size, output_dim=hidden_size, num_heads=num_heads,
                          use_proj_bias=use_proj_bias, use_separate_proj_weight=use_separate_proj_weight,
-                         compute_dtype=self.compute_dtype) for _ in range(message_passing_num)])
+                         compute_dtype=self.compute_dtype, dense=self.dense)
+             for _ in range(message_passing_num)])
         self._named = None
         _engine.flatten_parameters(self)
 
@@ -156,6 +164,12 @@ class EncodeTransformDecode(nn.Module):
         self.compute_dtype = dtype
         for blk in self.processor_list:
             blk.set_compute_dtype(dtype)
+        return self
+
+    def set_dense(self, dense):
+        self.dense = check_dense(dense)
+        for blk in self.processor_list:
+            blk.set_dense(dense)
         return self
 
     def _run(self, graph) -> torch.Tensor:

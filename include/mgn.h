@@ -585,6 +585,55 @@ int mgn_rollout_end(const float* out, const float* y, const float* x, int64_t N,
                     float* preds, int32_t capacity, int32_t* cursor, float* loss, float* sq, void* ws,
                     size_t ws_bytes, mgn_stream_t stream);
 
+/* ---------------------------------------------------------------- gated MLP (transformer block, dense half) */
+/* The second line of the reference's Transformer block (layers.py:198-262, 548-627), x + gated_mlp(norm2(x)):
+ *   n1 = scale_a ⊙ x / (‖x‖₂ · d^-½ + 1e-8)      n = scale_b ⊙ n1 / (‖n1‖₂ · d^-½ + 1e-8)     (d = norm_dim)
+ *   u = n W1ᵀ + b1,  v = n W2ᵀ + b2,  g = GELU(u) ⊙ v (erf GELU),  y = x + g W3ᵀ + b3
+ * x, y, dy, dx fp32 (x, y, dy with row strides >= hidden, dx [rows, hidden] contiguous). The descriptor points
+ * at the fp32 MASTER parameters, W1, W2 [expand, hidden] and W3 [hidden, expand] row-major without padding
+ * (nn.Linear weights), any 4-byte alignment: the kernels read them when they run (MGN_BF16 rounds them to bf16
+ * on the way into LDS), so a call issued — or a graph replayed — after an optimizer step sees the new values
+ * without a repack. MGN_F32: exact fp32 MFMA throughout. MGN_BF16: the GEMM operands (n, g, the weights, and
+ * dy, du, dv in the backward) are bf16, accumulation fp32; norms, u, v, GELU, the gate product, the residual,
+ * y, dx and every parameter gradient are fp32. hidden in [1, 256] is zero-padded to a kernel width inside the
+ * kernels; norm_dim (0: hidden) is the size the norms divide by.
+ *   _forward   saved NULL: inference. Else saved (mgn_gated_mlp_saved_bytes) receives the two row norms; u, v
+ *              and g are recomputed by the backward, nothing of size [rows, expand] is written by a forward.
+ *   _backward  dx and grads, the flat gradient in module parameter order {scale_a [h], scale_b [h], W1, b1, W2,
+ *              b2, W3, b3}, 2h + 9h² + 7h floats, overwritten. ws: mgn_gated_mlp_backward_workspace_bytes.
+ * Rows are processed in tiles of mgn_gated_mlp_row_tile() rows by mgn_gated_mlp_blocks(rows, max_blocks) =
+ * min(tiles, 512, max_blocks when > 0) workgroups, workgroup b the tiles b, b + blocks, ...; max_blocks leaves
+ * part of the device to other streams and does not change a result bit of y or dx (the scale gradients' column
+ * sums are added per workgroup, so their rounding follows the grid). The first call per device and kernel sets
+ * a function attribute (dynamic LDS): make one eager call before capturing a graph. Caller-owned memory, asynchronous on the stream, no host
+ * read-back (capturable), no atomics: every sum has a fixed order and two launches on the same inputs are
+ * bitwise equal; every workgroup is independent. rows == 0 returns 0 without a launch. Before any launch, a
+ * nonzero status (mgn_last_error) for hidden outside [1, 256], expand != 3·hidden, an unknown dtype, max_blocks < 0, a NULL
+ * required pointer, a row stride < hidden or a workspace too small. The added symbols do not change
+ * MGN_ABI_VERSION; MGN_HAS_GATED_MLP marks headers that declare them. */
+#define MGN_HAS_GATED_MLP 1
+typedef struct mgn_gated_mlp {
+    int32_t hidden, expand; /* expand == 3 * hidden */
+    int32_t dtype;          /* MGN_F32 | MGN_BF16 */
+    int32_t norm_dim;       /* 0: hidden */
+    int32_t max_blocks;     /* 0: the default grid; > 0: at most this many workgroups for the row-tile kernels */
+    int32_t reserved;       /* 0 */
+    const float *w1, *b1;   /* gated_mlp.1.linear1 [expand, hidden], [expand] */
+    const float *w2, *b2;   /* gated_mlp.1.linear2 */
+    const float *w3, *b3;   /* gated_mlp.2 [hidden, expand], [hidden] */
+    const float *scale_a;   /* norm2.scale [hidden] */
+    const float *scale_b;   /* gated_mlp.0.scale [hidden] */
+} mgn_gated_mlp;
+int32_t mgn_gated_mlp_row_tile(void);
+int32_t mgn_gated_mlp_blocks(int64_t rows, int32_t max_blocks);
+size_t mgn_gated_mlp_saved_bytes(const mgn_gated_mlp* m, int64_t rows);
+int mgn_gated_mlp_forward(const mgn_gated_mlp* m, const float* x, int64_t ldx, int64_t rows, float* y, int64_t ldy,
+                          void* saved, mgn_stream_t stream);
+size_t mgn_gated_mlp_backward_workspace_bytes(const mgn_gated_mlp* m, int64_t rows);
+int mgn_gated_mlp_backward(const mgn_gated_mlp* m, const float* x, int64_t ldx, int64_t rows, const void* saved,
+                           const float* dy, int64_t lddy, float* dx, float* grads, void* ws, size_t ws_bytes,
+                           mgn_stream_t stream);
+
 /* torch.optim.AdamW semantics (decoupled weight decay p *= 1 - lr*wd, bias-corrected moments,
  * denominator sqrt(v)/sqrt(1-beta2^t) + eps), fp32, over n contiguous elements. */
 int mgn_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
