@@ -13,6 +13,16 @@
 // their own load of the row brought in. The graph of a row is a binary search of graph_ptr (B + 1 ints,
 // the same few cache lines for every thread). The noisy ranges ride in the kernel arguments; the loop over
 // them is unrolled with constant indices, so they stay in scalar registers.
+//
+// Rotation augmentation (the reference's Random3DRotate, dataset/preprocessing.py:277-366, one rotation per
+// graph): feed_batch_rot is feed_batch with column triples and R [B, 9] (row-major 3x3 per graph, written
+// by rotation_matrices from three angles). The thread of a column c of triple (s, s + 3) reads the three
+// source values of its row — the cache line its own value sits on — and writes row vector times matrix,
+// (a0·R[0][c-s] + a1·R[1][c-s]) + a2·R[2][c-s], every product and sum rounded on its own and in that order,
+// so that the same expression written with torch's elementwise ops gives the same bits. Noise comes second.
+// The thread of a y column does the same with the y columns of the next frame. rotate_rows is the rule on
+// the rows of a [rows, cols] matrix (edge_attr) whose graph comes from row_graph. All of it stays one
+// element per thread on consecutive floats, for the reasons above: a handful of loads and five flops.
 #include "mgn_common.h"
 
 namespace {
@@ -60,6 +70,159 @@ __global__ __launch_bounds__(256) void feed_batch(const float* __restrict__ traj
     if (c >= y_start && c < y_end) y[r * ldy + (c - y_start)] = src[(int64_t)N * F + c];
 }
 
+// (a0·R[0][j] + a1·R[1][j]) + a2·R[2][j], R the row-major 3x3 at Rg: plain operators, the caller's function
+// body is under fp contract(off) and so is this one (see feed_batch on __fmul_rn / __fadd_rn)
+__device__ __forceinline__ float rot3(const float* __restrict__ a, const float* __restrict__ Rg, int j) {
+#pragma clang fp contract(off)
+    const float p0 = a[0] * Rg[j];
+    const float p1 = a[1] * Rg[3 + j];
+    const float p2 = a[2] * Rg[6 + j];
+    const float s01 = p0 + p1;
+    return s01 + p2;
+}
+
+// start of the triple that holds column c, or -1
+__device__ __forceinline__ int triple_of(const mgn_feed_ranges& tr, int c) {
+    int s = -1;
+#pragma unroll
+    for (int i = 0; i < MGN_FEED_MAX_RANGES; ++i)
+        if (i < tr.n && c >= tr.start[i] && c < tr.start[i] + 3) s = tr.start[i];
+    return s;
+}
+
+__global__ __launch_bounds__(64) void rotation_matrices(const float* __restrict__ angles, int B,
+                                                        float* __restrict__ R) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= B) return;
+    float sa, ca, sb, cb, sg, cg;
+    sincosf(angles[3 * g + 0], &sa, &ca);  // alpha: about z
+    sincosf(angles[3 * g + 1], &sb, &cb);  // beta: about y
+    sincosf(angles[3 * g + 2], &sg, &cg);  // gamma: about x
+    float* o = R + 9 * (int64_t)g;
+    o[0] = ca * cb;
+    o[1] = ca * sb * sg + sa * cg;
+    o[2] = -ca * sb * cg + sa * sg;
+    o[3] = -sa * cb;
+    o[4] = -sa * sb * sg + ca * cg;
+    o[5] = sa * sb * cg + ca * sg;
+    o[6] = sb;
+    o[7] = -cb * sg;
+    o[8] = cb * cg;
+}
+
+// feed_batch with the rotation in front of the noise; tr.n >= 1 (the host sends tr.n == 0 to feed_batch)
+__global__ __launch_bounds__(256) void feed_batch_rot(const float* __restrict__ traj, int64_t N, int F,
+                                                      const int32_t* __restrict__ graph_ptr, int B,
+                                                      const int32_t* __restrict__ frame, int y_start, int y_end,
+                                                      int type_index, mgn_feed_ranges rg,
+                                                      const float* __restrict__ scales,
+                                                      const float* __restrict__ z, int64_t ldz,
+                                                      float* __restrict__ x, int64_t ldx, float* __restrict__ y,
+                                                      int64_t ldy, mgn_feed_ranges tr,
+                                                      const float* __restrict__ R) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t total = N * F;
+    if (e >= total) return;
+    int64_t r;
+    if (total <= (int64_t)UINT32_MAX)
+        r = (uint32_t)e / (uint32_t)F;
+    else
+        r = e / F;
+    const int c = (int)(e - r * F);
+    const int g = graph_of_row(graph_ptr, B, r);
+    const int64_t t = frame[g];
+    const float* src = traj + (t * N + r) * F;
+    const float* Rg = R + 9 * (int64_t)g;
+    float v = src[c];
+    const int ts = triple_of(tr, c);
+    if (ts >= 0) v = rot3(src + ts, Rg, c - ts);
+    if (z != nullptr) {
+        int zc = -1, which = 0, w = 0;
+#pragma unroll
+        for (int i = 0; i < MGN_FEED_MAX_RANGES; ++i)
+            if (i < rg.n) {
+                if (c >= rg.start[i] && c < rg.end[i]) {
+                    zc = w + c - rg.start[i];
+                    which = i;
+                }
+                w += rg.end[i] - rg.start[i];
+            }
+        if (zc >= 0 && src[type_index] == 0.f) {  // type_index lies in no triple: the clean node type
+            const float noise = z[r * ldz + zc] * scales[which];
+            v = v + noise;
+        }
+    }
+    x[r * ldx + c] = v;
+    // the y range is 3 wide here (checked on the host): the rotated y columns of the next clean frame
+    if (c >= y_start && c < y_end) y[r * ldy + (c - y_start)] = rot3(src + (int64_t)N * F + y_start, Rg, c - y_start);
+}
+
+__global__ __launch_bounds__(256) void rotate_rows(const float* __restrict__ src, int64_t rows, int cols,
+                                                   int64_t ld_src, const int32_t* __restrict__ row_graph, int B,
+                                                   mgn_feed_ranges tr, const float* __restrict__ R,
+                                                   float* __restrict__ dst, int64_t ld_dst) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t total = rows * cols;
+    if (e >= total) return;
+    int64_t r;
+    if (total <= (int64_t)UINT32_MAX)
+        r = (uint32_t)e / (uint32_t)cols;
+    else
+        r = e / cols;
+    const int c = (int)(e - r * cols);
+    const float* a = src + r * ld_src;
+    float v = a[c];
+    const int ts = triple_of(tr, c);
+    if (ts >= 0) {
+        const int g = row_graph[r];
+        if (g >= 0 && g < B) v = rot3(a + ts, R + 9 * (int64_t)g, c - ts);  // else: copied, R is not read
+    }
+    dst[r * ld_dst + c] = v;
+}
+
+// The host-side checks of column triples against a row of `width` columns; 0 or the status of MGN_REQUIRE.
+int check_triples(const std::string& who, const mgn_feed_ranges& tr, int64_t width, const char* width_name) {
+    MGN_REQUIRE(tr.n >= 0 && tr.n <= MGN_FEED_MAX_RANGES, who + ": at most 4 column triples");
+    for (int i = 0; i < tr.n; ++i) {
+        MGN_REQUIRE(tr.end[i] - (int64_t)tr.start[i] == 3, who + ": a column triple must be exactly 3 columns wide");
+        MGN_REQUIRE(tr.start[i] >= 0 && tr.end[i] <= width,
+                    who + ": a column triple is outside [0, " + width_name + ")");
+        for (int j = 0; j < i; ++j)
+            MGN_REQUIRE(tr.start[i] >= tr.end[j] || tr.start[j] >= tr.end[i], who + ": column triples overlap");
+    }
+    return 0;
+}
+
+// Every argument check mgn_feed_batch makes ahead of its N == 0 return; *W: the noisy column count.
+int check_feed(const std::string& who, int64_t T, int64_t N, int32_t F, int32_t B, int32_t y_start, int32_t y_end,
+               int32_t type_index, const mgn_feed_ranges& ranges, const float* z, int64_t ldz, int64_t ldx,
+               int64_t ldy, int64_t* W_out) {
+    MGN_REQUIRE(T >= 2, who + ": a trajectory needs at least 2 frames (x from frame t, y from t + 1)");
+    MGN_REQUIRE(F >= 1, who + ": F must be >= 1");
+    MGN_REQUIRE(N >= 0 && B >= 0, who + ": N and B must be >= 0");
+    MGN_REQUIRE(N <= INT32_MAX, who + ": graph_ptr is int32, N must fit it");
+    MGN_REQUIRE(ranges.n >= 0 && ranges.n <= MGN_FEED_MAX_RANGES, who + ": at most 4 noisy column ranges");
+    int64_t W = 0;
+    for (int i = 0; i < ranges.n; ++i) {
+        MGN_REQUIRE(ranges.start[i] >= 0 && ranges.start[i] <= ranges.end[i] && ranges.end[i] <= F,
+                    who + ": a noisy column range is outside [0, F]");
+        for (int j = 0; j < i; ++j)
+            MGN_REQUIRE(ranges.start[i] >= ranges.end[j] || ranges.start[j] >= ranges.end[i] ||
+                            ranges.start[i] == ranges.end[i] || ranges.start[j] == ranges.end[j],
+                        who + ": noisy column ranges overlap");
+        W += ranges.end[i] - ranges.start[i];
+    }
+    MGN_REQUIRE(y_start >= 0 && y_start <= y_end && y_end <= F, who + ": the y column range is outside [0, F]");
+    MGN_REQUIRE(type_index >= 0 && type_index < F, who + ": type_index is outside [0, F)");
+    MGN_REQUIRE(ldx >= F, who + ": ldx is smaller than F");
+    MGN_REQUIRE(ldy >= y_end - y_start, who + ": ldy is smaller than the y column count");
+    MGN_REQUIRE(z == nullptr || ldz >= W, who + ": ldz is smaller than the noisy column count");
+    *W_out = W;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -68,26 +231,9 @@ int mgn_feed_batch(const float* traj, int64_t T, int64_t N, int32_t F, const int
                    const int32_t* frame, int32_t y_start, int32_t y_end, int32_t type_index, mgn_feed_ranges ranges,
                    const float* scales, const float* z, int64_t ldz, float* x, int64_t ldx, float* y, int64_t ldy,
                    mgn_stream_t stream) {
-    MGN_REQUIRE(T >= 2, "feed_batch: a trajectory needs at least 2 frames (x from frame t, y from t + 1)");
-    MGN_REQUIRE(F >= 1, "feed_batch: F must be >= 1");
-    MGN_REQUIRE(N >= 0 && B >= 0, "feed_batch: N and B must be >= 0");
-    MGN_REQUIRE(N <= INT32_MAX, "feed_batch: graph_ptr is int32, N must fit it");
-    MGN_REQUIRE(ranges.n >= 0 && ranges.n <= MGN_FEED_MAX_RANGES, "feed_batch: at most 4 noisy column ranges");
     int64_t W = 0;
-    for (int i = 0; i < ranges.n; ++i) {
-        MGN_REQUIRE(ranges.start[i] >= 0 && ranges.start[i] <= ranges.end[i] && ranges.end[i] <= F,
-                    "feed_batch: a noisy column range is outside [0, F]");
-        for (int j = 0; j < i; ++j)
-            MGN_REQUIRE(ranges.start[i] >= ranges.end[j] || ranges.start[j] >= ranges.end[i] ||
-                            ranges.start[i] == ranges.end[i] || ranges.start[j] == ranges.end[j],
-                        "feed_batch: noisy column ranges overlap");
-        W += ranges.end[i] - ranges.start[i];
-    }
-    MGN_REQUIRE(y_start >= 0 && y_start <= y_end && y_end <= F, "feed_batch: the y column range is outside [0, F]");
-    MGN_REQUIRE(type_index >= 0 && type_index < F, "feed_batch: type_index is outside [0, F)");
-    MGN_REQUIRE(ldx >= F, "feed_batch: ldx is smaller than F");
-    MGN_REQUIRE(ldy >= y_end - y_start, "feed_batch: ldy is smaller than the y column count");
-    MGN_REQUIRE(z == nullptr || ldz >= W, "feed_batch: ldz is smaller than the noisy column count");
+    if (int rc = check_feed("feed_batch", T, N, F, B, y_start, y_end, type_index, ranges, z, ldz, ldx, ldy, &W))
+        return rc;
     if (N == 0 || B == 0) return 0;
     MGN_REQUIRE(traj && graph_ptr && frame && x && (y || y_start == y_end), "feed_batch: a null pointer argument");
     MGN_REQUIRE(z == nullptr || W == 0 || scales != nullptr, "feed_batch: noise (z) without scales");
@@ -96,6 +242,71 @@ int mgn_feed_batch(const float* traj, int64_t T, int64_t N, int32_t F, const int
     hipLaunchKernelGGL(feed_batch, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, traj, N, (int)F,
                        graph_ptr, (int)B, frame, (int)y_start, (int)y_end, (int)type_index, ranges, scales,
                        W > 0 ? z : nullptr, ldz, x, ldx, y, ldy);
+    MGN_LAUNCH_CHECK();
+    return 0;
+}
+
+int mgn_feed_rotation_matrices(const float* angles, int32_t B, float* R, mgn_stream_t stream) {
+    MGN_REQUIRE(B >= 0, "feed_rotation_matrices: B must be >= 0");
+    if (B == 0) return 0;
+    MGN_REQUIRE(angles && R, "feed_rotation_matrices: a null pointer argument");
+    hipLaunchKernelGGL(rotation_matrices, dim3((unsigned)cdiv64(B, 64)), dim3(64), 0, (hipStream_t)stream, angles,
+                       (int)B, R);
+    MGN_LAUNCH_CHECK();
+    return 0;
+}
+
+int mgn_feed_batch_rot(const float* traj, int64_t T, int64_t N, int32_t F, const int32_t* graph_ptr, int32_t B,
+                       const int32_t* frame, int32_t y_start, int32_t y_end, int32_t type_index,
+                       mgn_feed_ranges ranges, const float* scales, const float* z, int64_t ldz, float* x, int64_t ldx,
+                       float* y, int64_t ldy, mgn_feed_ranges triples, const float* R, mgn_stream_t stream) {
+    int64_t W = 0;
+    if (int rc = check_feed("feed_batch_rot", T, N, F, B, y_start, y_end, type_index, ranges, z, ldz, ldx, ldy, &W))
+        return rc;
+    if (int rc = check_triples("feed_batch_rot", triples, F, "F")) return rc;
+    for (int i = 0; i < triples.n; ++i)
+        MGN_REQUIRE(type_index < triples.start[i] || type_index >= triples.end[i],
+                    "feed_batch_rot: type_index lies inside a column triple");
+    if (triples.n > 0) {
+        MGN_REQUIRE(y_end - y_start == 0 || y_end - y_start == 3,
+                    "feed_batch_rot: with column triples the y column range must be 3 wide (or empty)");
+        MGN_REQUIRE(R != nullptr, "feed_batch_rot: column triples without R");
+    }
+    if (N == 0 || B == 0) return 0;
+    MGN_REQUIRE(traj && graph_ptr && frame && x && (y || y_start == y_end), "feed_batch_rot: a null pointer argument");
+    MGN_REQUIRE(z == nullptr || W == 0 || scales != nullptr, "feed_batch_rot: noise (z) without scales");
+    const int64_t blocks = cdiv64(N * F, 256);
+    MGN_REQUIRE(blocks <= INT32_MAX, "feed_batch_rot: N * F is too large for one launch");
+    if (triples.n == 0)  // no rotation: mgn_feed_batch's own kernel, so exactly its result
+        hipLaunchKernelGGL(feed_batch, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, traj, N, (int)F,
+                           graph_ptr, (int)B, frame, (int)y_start, (int)y_end, (int)type_index, ranges, scales,
+                           W > 0 ? z : nullptr, ldz, x, ldx, y, ldy);
+    else
+        hipLaunchKernelGGL(feed_batch_rot, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, traj, N, (int)F,
+                           graph_ptr, (int)B, frame, (int)y_start, (int)y_end, (int)type_index, ranges, scales,
+                           W > 0 ? z : nullptr, ldz, x, ldx, y, ldy, triples, R);
+    MGN_LAUNCH_CHECK();
+    return 0;
+}
+
+int mgn_feed_rotate_rows(const float* src, int64_t rows, int32_t cols, int64_t ld_src, const int32_t* row_graph,
+                         int32_t B, mgn_feed_ranges triples, const float* R, float* dst, int64_t ld_dst,
+                         mgn_stream_t stream) {
+    MGN_REQUIRE(rows >= 0 && B >= 0, "feed_rotate_rows: rows and B must be >= 0");
+    MGN_REQUIRE(cols >= 1, "feed_rotate_rows: cols must be >= 1");
+    if (int rc = check_triples("feed_rotate_rows", triples, cols, "cols")) return rc;
+    MGN_REQUIRE(triples.n == 0 || R != nullptr, "feed_rotate_rows: column triples without R");
+    MGN_REQUIRE(ld_src >= cols, "feed_rotate_rows: ld_src is smaller than cols");
+    MGN_REQUIRE(ld_dst >= cols, "feed_rotate_rows: ld_dst is smaller than cols");
+    if (rows == 0) return 0;
+    MGN_REQUIRE(src && dst && (row_graph || triples.n == 0), "feed_rotate_rows: a null pointer argument");
+    // a thread reads the three source values of its triple and writes one of them: in place would race
+    MGN_REQUIRE(src + ((rows - 1) * ld_src + cols) <= dst || dst + ((rows - 1) * ld_dst + cols) <= src,
+                "feed_rotate_rows: src and dst overlap");
+    const int64_t blocks = cdiv64(rows * cols, 256);
+    MGN_REQUIRE(blocks <= INT32_MAX, "feed_rotate_rows: rows * cols is too large for one launch");
+    hipLaunchKernelGGL(rotate_rows, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, rows, (int)cols,
+                       ld_src, row_graph, (int)B, triples, R, dst, ld_dst);
     MGN_LAUNCH_CHECK();
     return 0;
 }

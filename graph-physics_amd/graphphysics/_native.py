@@ -182,6 +182,10 @@ EXPORTS = {
     "mgn_gmm_sample_diag": (_i32, [_vp, _i64, _i32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "mgn_feed_batch": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _i32, FeedRanges, _vp, _vp, _i64,
                               _vp, _i64, _vp, _i64, _vp]),
+    "mgn_feed_rotation_matrices": (_i32, [_vp, _i32, _vp, _vp]),
+    "mgn_feed_batch_rot": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _i32, FeedRanges, _vp, _vp,
+                                  _i64, _vp, _i64, _vp, _i64, FeedRanges, _vp, _vp]),
+    "mgn_feed_rotate_rows": (_i32, [_vp, _i64, _i32, _i64, _vp, _i32, FeedRanges, _vp, _vp, _i64, _vp]),
     "mgn_rollout_begin": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
                                  _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "mgn_rollout_end_workspace_bytes": (_sz, [_i64]),
@@ -502,14 +506,20 @@ def feed_ranges(ranges):
     return r
 
 
-def feed_batch(traj, graph_ptr, frame, y_columns, type_index, ranges, scales, z, x, y):
+def feed_batch(traj, graph_ptr, frame, y_columns, type_index, ranges, scales, z, x, y, triples=None, R=None):
     """One training batch from resident trajectories (mgn_feed_batch): x[:, :F] = frame[g] of traj [T, N, F]
     for the nodes of graph g, plus z * scales on the noisy column ranges of NORMAL rows; y = columns
     y_columns of the next clean frame. graph_ptr / frame: int32 device tensors [B+1] / [B]; z None: no
-    noise. Writes x and y in place (x may be wider than F) on the current stream."""
+    noise. Writes x and y in place (x may be wider than F) on the current stream. triples (column triples
+    [(s, s + 3), ...] or a FeedRanges) and R (fp32 [B, 9]): mgn_feed_batch_rot, the triples of x and y rotated
+    by R[g] ahead of the noise."""
     import torch
 
     require_device(traj)
+    if triples is not None and (triples.n if isinstance(triples, FeedRanges) else len(triples)) > 0:
+        if R is None or R.dtype != torch.float32 or not R.is_contiguous() or R.device != traj.device or \
+                tuple(R.shape) != (frame.numel(), 9):
+            raise ValueError(f"feed_batch: R must be a contiguous fp32 [{frame.numel()}, 9] tensor on traj's device")
     if traj.dtype != torch.float32 or traj.dim() != 3 or not traj.is_contiguous():
         raise ValueError("feed_batch: traj must be a contiguous fp32 [T, N, F] tensor")
     T, N, F = traj.shape
@@ -523,10 +533,53 @@ def feed_batch(traj, graph_ptr, frame, y_columns, type_index, ranges, scales, z,
     if x.shape[1] < F or y.shape[1] != y_columns[1] - y_columns[0]:
         raise ValueError("feed_batch: x needs at least F columns and y exactly y_columns[1] - y_columns[0]")
     rg = ranges if isinstance(ranges, FeedRanges) else feed_ranges(ranges)
-    check(lib().mgn_feed_batch(ptr(traj), T, N, F, ptr(graph_ptr), frame.numel(), ptr(frame), int(y_columns[0]),
-                               int(y_columns[1]), int(type_index), rg, ptr(scales), ptr(z),
-                               z.stride(0) if z is not None else 0, ptr(x), x.stride(0), ptr(y), y.stride(0),
-                               stream_ptr(traj.device)))
+    args = (ptr(traj), T, N, F, ptr(graph_ptr), frame.numel(), ptr(frame), int(y_columns[0]), int(y_columns[1]),
+            int(type_index), rg, ptr(scales), ptr(z), z.stride(0) if z is not None else 0, ptr(x), x.stride(0),
+            ptr(y), y.stride(0))
+    if triples is None:
+        check(lib().mgn_feed_batch(*args, stream_ptr(traj.device)))
+    else:
+        tr = triples if isinstance(triples, FeedRanges) else feed_ranges(triples)
+        check(lib().mgn_feed_batch_rot(*args, tr, ptr(R), stream_ptr(traj.device)))
+
+
+def feed_rotation_matrices(angles, R):
+    """R[g] = the reference's _build_rotation_matrix(*angles[g]) in fp32, row-major (mgn_feed_rotation_matrices).
+    angles fp32 [B, 3] in radians {alpha (z), beta (y), gamma (x)}, R fp32 [B, 9], both contiguous on one HIP
+    device; written in place on the current stream."""
+    import torch
+
+    require_device(angles)
+    B = angles.shape[0]
+    ok = angles.dtype == torch.float32 and R.dtype == torch.float32 and tuple(angles.shape) == (B, 3) and \
+        tuple(R.shape) == (B, 9) and angles.is_contiguous() and R.is_contiguous() and R.device == angles.device
+    if not ok:
+        raise ValueError("feed_rotation_matrices: angles [B, 3] and R [B, 9] must be contiguous fp32 tensors on one "
+                         "device")
+    check(lib().mgn_feed_rotation_matrices(ptr(angles), B, ptr(R), stream_ptr(angles.device)))
+
+
+def feed_rotate_rows(src, row_graph, triples, R, dst):
+    """dst[:, :cols] = the rows of src [rows, cols] with the column triples rotated by R[row_graph[r]]
+    (mgn_feed_rotate_rows); other columns, and rows whose graph id is outside [0, B), are copied. dst may be
+    wider than src; src and dst must not overlap. On the current stream."""
+    import torch
+
+    require_device(src)
+    rows, cols = src.shape
+    for name, t in (("src", src), ("dst", dst)):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != rows or t.device != src.device or \
+                (t.shape[1] > 1 and t.stride(1) != 1) or t.shape[1] < cols:
+            raise ValueError(f"feed_rotate_rows: {name} must be an fp32 [{rows}, >= {cols}] tensor on src's device "
+                             "with unit column stride")
+    if row_graph.dtype != torch.int32 or row_graph.numel() != rows or not row_graph.is_contiguous() or \
+            row_graph.device != src.device:
+        raise ValueError(f"feed_rotate_rows: row_graph must be a contiguous int32 tensor of {rows} elements")
+    if R.dtype != torch.float32 or R.dim() != 2 or R.shape[1] != 9 or not R.is_contiguous() or R.device != src.device:
+        raise ValueError("feed_rotate_rows: R must be a contiguous fp32 [B, 9] tensor on src's device")
+    tr = triples if isinstance(triples, FeedRanges) else feed_ranges(triples)
+    check(lib().mgn_feed_rotate_rows(ptr(src), rows, cols, src.stride(0), ptr(row_graph), R.shape[0], tr, ptr(R),
+                                     ptr(dst), dst.stride(0), stream_ptr(src.device)))
 
 
 def _rollout_2d(fn, name, t, rows, dev, cols=None):

@@ -9,14 +9,21 @@ device (graphphysics.utils.graph_build), the O(N) feature edits as device torch 
   add_world_edges          preprocessing.py:92-140  (cKDTree.query_pairs → grid radius search)
   add_world_pos_features   preprocessing.py:143-174
   add_noise                preprocessing.py:177-238
+  Random3DRotate           preprocessing.py:277-366 (one random rotation of pos, triples of x, and y)
   build_preprocessing      preprocessing.py:369-440 (noise, world-pos and edge-feature stages)
 
-Random3DRotate / compute_min_distance_to_type (augmentation / aneurysm features) are outside the
-MGN hot path and are not provided.
+Random3DRotate is the per-item transform, for a host-side pipeline (an entry of extra_node_features). Inside a
+captured training step the same augmentation is drawn and applied on the device by the resident feed:
+dataset.resident.ResidentTrajectories(..., rotate=...).
+
+compute_min_distance_to_type (a one-off aneurysm feature builder, not per-step work) is outside the MGN hot
+path and is not provided.
 """
+import copy
 import math
+import random
 from functools import partial
-from typing import Callable, List, Optional, Union
+from typing import Callable, List, Optional, Tuple, Union
 
 import torch
 
@@ -89,6 +96,61 @@ def add_noise(graph, noise_index_start: Union[int, List[int]], noise_index_end: 
         noise[mask] = 0
         graph.x[:, start:end] = feature + noise
     return graph
+
+
+class Random3DRotate:
+    """The reference's Random3DRotate: one random 3D rotation applied to the node positions, to the 3-column
+    ranges `feature_indices` of graph.x, and to the first 3 columns of graph.y. Row vectors times the matrix
+    (v @ R), torch ops on whatever device the tensors are on. As in the reference, x is written in place while
+    pos and y are rebound to new tensors, and a y wider than 3 columns comes back 3 wide."""
+
+    def __init__(self, feature_indices: List[Tuple[int, int]] = None) -> None:
+        self.feature_indices = feature_indices or []
+        for s, e in self.feature_indices:
+            assert e - s == 3, f"a rotated feature range holds the 3 columns of one xyz vector, got ({s}, {e})"
+
+    def _get_random_angles(self):
+        """[alpha (about z), beta (about y), gamma (about x)] in radians: three draws of
+        random.uniform(-180, 180) degrees, in that order."""
+        return [math.radians(random.uniform(-180, 180)) for _ in range(3)]
+
+    def _build_rotation_matrix(self, alpha, beta, gamma):
+        """The reference's 3x3 matrix of yaw alpha, pitch beta and roll gamma (radians), computed in Python
+        floats with its order of operations, as a torch tensor of the default dtype."""
+        ca, sa = math.cos(alpha), math.sin(alpha)
+        cb, sb = math.cos(beta), math.sin(beta)
+        cg, sg = math.cos(gamma), math.sin(gamma)
+        return torch.tensor([[ca * cb, ca * sb * sg + sa * cg, -ca * sb * cg + sa * sg],
+                             [-sa * cb, -sa * sb * sg + ca * cg, sa * sb * cg + ca * sg],
+                             [sb, -cb * sg, cb * cg]])
+
+    def _rotate_features(self, x: torch.Tensor, matrix: torch.Tensor) -> torch.Tensor:
+        """x with every range of feature_indices replaced by range @ matrix; written in place."""
+        m = matrix.to(x.device, x.dtype)
+        for s, e in self.feature_indices:
+            x[:, s:e] = x[:, s:e] @ m
+        return x
+
+    def forward(self, data):
+        R = self._build_rotation_matrix(*self._get_random_angles())
+        pos = getattr(data, "pos", None)
+        if pos is not None:
+            pos = pos.view(-1, 1) if pos.dim() == 1 else pos
+            assert pos.size(-1) == 3, "Node positions must be 3-dimensional"
+            data.pos = pos @ R.to(pos.device, pos.dtype)
+        if getattr(data, "x", None) is not None and self.feature_indices:
+            data.x = self._rotate_features(data.x, R)
+        if hasattr(data, "y") and data.x is not None:  # the reference's condition; only the first 3 columns stay
+            y = data.y[:, 0:3]
+            data.y = y @ R.to(y.device, y.dtype)
+        return data
+
+    def __call__(self, data):
+        # torch_geometric's BaseTransform: forward on a shallow copy, so pos and y are rebound on the copy only
+        return self.forward(copy.copy(data))
+
+    def __repr__(self) -> str:
+        return f"{self.__class__.__name__}({self.feature_indices})"
 
 
 def build_preprocessing(noise_parameters: Optional[dict] = None, world_pos_parameters: Optional[dict] = None,

@@ -11,8 +11,16 @@ The stored frames are only ever read: the in-place write of preprocessing.add_no
 on the device, would pile noise on noise epoch after epoch (the reference re-reads every item from disk and
 never sees this); here the noise goes into the batch, never into `traj`.
 
+Rotation augmentation (rotate=; the reference's Random3DRotate, dataset/preprocessing.py:277-366) lives where
+the noise lives: three angles per graph drawn on the device, a matrix per graph (mgn_feed_rotation_matrices),
+the column triples of x and the 3 columns of y rotated by the fill's own launch ahead of the noise
+(mgn_feed_batch_rot), and the triples of a clean edge_attr rotated into the batch's by one more launch
+(mgn_feed_rotate_rows). The rule is row vector times matrix written term by term, (a0·R0j + a1·R1j) + a2·R2j,
+so the torch ops of fill_torch / rotate_rows_torch give the kernels' bits.
+
 Not supported: `previous_data`, per-frame positions or edge_attr (Lagrangian datasets), and trajectories of
-unequal length in one batch. batch.edge_index / edge_attr are never touched.
+unequal length in one batch. batch.edge_index is never touched, batch.edge_attr only by a rotating feed that
+was given a clean edge_attr.
 
 The validation rollout reads the same resident frames (training.rollout.Rollout.rollout_resident):
 rollout_begin_torch / rollout_end_torch state, as torch ops on any device, the two rules libmgn's
@@ -54,23 +62,78 @@ def _check_ranges(ranges, F):
                 raise ValueError(f"noisy column ranges ({s2}, {e2}) and ({s}, {e}) overlap")
 
 
+def _check_triples(triples, width, name, what):
+    """[(s, s + 3), ...] as ints, after the checks of a rotation's column triples (ValueError)."""
+    try:
+        triples = [(int(s), int(e)) for s, e in triples]
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a list of (start, end) column pairs, got {triples!r}") from None
+    if len(triples) > nat.MGN_FEED_MAX_RANGES:
+        raise ValueError(f"at most {nat.MGN_FEED_MAX_RANGES} column triples are supported, got {len(triples)}")
+    for i, (s, e) in enumerate(triples):
+        if e - s != 3:
+            raise ValueError(f"each range of {name} must span exactly 3 columns (xyz), got ({s}, {e})")
+        if not 0 <= s < e <= width:
+            raise ValueError(f"column triple ({s}, {e}) is outside the {width} columns of {what}")
+        for s2, e2 in triples[:i]:
+            if s < e2 and s2 < e:
+                raise ValueError(f"column triples ({s2}, {e2}) and ({s}, {e}) overlap")
+    return triples
+
+
 def _node_graph(graph_ptr, N, device):
     """Graph id of every node from node offsets [B+1] (a host list or a tensor)."""
     gp = torch.as_tensor(graph_ptr, dtype=torch.int64).to(device)
     return torch.repeat_interleave(torch.arange(gp.numel() - 1, device=device), gp[1:] - gp[:-1], output_size=N)
 
 
-def fill_torch(traj, graph_ptr, frame, y_columns, node_type_index, ranges, scales, z):
+def _rot3(a, Rm):
+    """Row vectors a [n, 3] times the per-row matrices Rm [n, 3, 3] as the kernels write it, term by term:
+    (a0·R[0][j] + a1·R[1][j]) + a2·R[2][j]. Elementwise ops round every product and every sum on their own,
+    which a matmul (BLAS may fuse multiply-adds, and orders the sum as it likes) does not promise."""
+    return (a[:, 0:1] * Rm[:, 0] + a[:, 1:2] * Rm[:, 1]) + a[:, 2:3] * Rm[:, 2]
+
+
+def rotate_rows_torch(src, row_graph, triples, R):
+    """mgn_feed_rotate_rows' rule as torch ops on any device: a new tensor, src [rows, cols] with the columns of
+    every triple (s, s + 3) of row r rotated by R[row_graph[r]] (R [B, 9], row-major 3x3 per graph); other
+    columns, and the rows whose graph id is outside [0, B), are src bit for bit."""
+    out = src.clone()
+    B = R.shape[0]
+    if src.shape[0] == 0 or B == 0:
+        return out
+    g = row_graph.to(src.device, torch.int64)
+    valid = ((g >= 0) & (g < B))[:, None]
+    Rm = R.to(src.device)[g.clamp(0, B - 1)].view(-1, 3, 3)
+    for s, e in triples:
+        a = src[:, s:e]
+        out[:, s:e] = torch.where(valid, _rot3(a, Rm), a)
+    return out
+
+
+def fill_torch(traj, graph_ptr, frame, y_columns, node_type_index, ranges, scales, z, triples=None, R=None):
     """mgn_feed_batch's rule as torch ops on any device: returns (x [N, F], y [N, y_end - y_start]) as new
     tensors. x = frame[g] of traj for the nodes of graph g, plus z[:, zc] * scales[i] on the columns of
     noisy range i of the rows whose (clean) node type is NORMAL — zc runs over the ranges in order; y = the
-    y_columns of the next clean frame. z None: no noise. What ResidentTrajectories.fill runs on CPU tensors,
-    and what the kernel is tested and timed against."""
+    y_columns of the next clean frame. z None: no noise. triples [(s, s + 3), ...] and R [B, 9]
+    (mgn_feed_batch_rot's rule): the columns of every triple of x, and y (3 wide then), are rotated by the
+    matrix of the row's graph, before the noise. What ResidentTrajectories.fill runs on CPU tensors, and what
+    the kernels are tested and timed against."""
     T, N, F = traj.shape
     rows = torch.arange(N, device=traj.device)
-    t = frame.to(traj.device, torch.int64)[_node_graph(graph_ptr, N, traj.device)]
+    node_graph = _node_graph(graph_ptr, N, traj.device)
+    t = frame.to(traj.device, torch.int64)[node_graph]
     x = traj[t, rows]
     y = traj[t + 1, rows, y_columns[0]:y_columns[1]].contiguous()
+    if triples:
+        if R is None:
+            raise ValueError("column triples without R")
+        if y_columns[1] - y_columns[0] != 3:
+            raise ValueError(f"with column triples y_columns {tuple(y_columns)} must be 3 wide")
+        Rm = R.to(traj.device)[node_graph].view(-1, 3, 3)
+        for s, e in triples:  # triples do not overlap: each reads its own three clean columns
+            x[:, s:e] = _rot3(x[:, s:e], Rm)
+        y = _rot3(y, Rm)
     if z is not None:
         normal = (x[:, node_type_index] == NodeType.NORMAL)[:, None]
         zc = 0
@@ -163,9 +226,23 @@ class ResidentTrajectories:
     frame [B] int32, z [N, W] fp32 (None without noise) and scales [n] fp32 (None without noise) are
     allocated once and only rewritten: a captured graph keeps reading the same addresses, tests and users
     read there what the last fill used. Not supported: previous_data, per-frame positions or edge_attr,
-    trajectories of unequal length (module docstring)."""
+    trajectories of unequal length (module docstring).
 
-    def __init__(self, traj, graph_ptr, y_columns, node_type_index, noise=None, frames="random"):
+    rotate: None, or the rotation augmentation of the reference's Random3DRotate, one rotation per graph and
+    fill, as a dict
+      {"feature_indices": [(0, 3), (4, 7)],   # column triples of x (its argument); list position columns too
+       "edge_attr": clean_edge_attr,          # optional: fp32 [E, A] kept clean on the device
+       "edge_index": edge_index,              # required with edge_attr: [2, E]
+       "edge_feature_indices": [(0, 3)]}      # column triples of edge_attr; default [(0, 3)]
+    y_columns must be 3 wide then: y is rotated too. angles [B, 3] (radians: alpha about z, beta about y,
+    gamma about x) and R [B, 9] (row-major 3x3 per graph) are persistent like frame and z; row_graph [E] int32
+    is the graph of every edge, built once. fill writes the rotated edge_attr into batch.edge_attr[:, :A]; the
+    clean edge_attr, like traj, is only read. batch.pos is not touched (no model here reads it in the step).
+    See set_rotations."""
+
+    ROTATE_KEYS = ("feature_indices", "edge_attr", "edge_index", "edge_feature_indices")
+
+    def __init__(self, traj, graph_ptr, y_columns, node_type_index, noise=None, frames="random", rotate=None):
         if not torch.is_tensor(traj) or traj.dtype != torch.float32 or traj.dim() != 3 or not traj.is_contiguous():
             raise ValueError("traj must be a contiguous fp32 [T, N, F] tensor")
         T, N, F = traj.shape
@@ -199,6 +276,70 @@ class ResidentTrajectories:
         self.frame = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.random_frames = True
         self.set_frames(frames)
+        self.triples, self.angles, self.R = [], None, None
+        self.edge_attr, self.edge_triples, self.row_graph = None, [], None
+        self.random_rotations = None  # None: no rotation; True: drawn on every fill; False: explicit angles
+        if rotate is not None:
+            self._init_rotate(rotate, gp)
+
+    def _init_rotate(self, rotate, gp):
+        if not isinstance(rotate, dict) or any(k not in self.ROTATE_KEYS for k in rotate):
+            raise ValueError(f"rotate must be a dict with keys among {self.ROTATE_KEYS}, got {rotate!r}")
+        dev, k = self.traj.device, self.node_type_index
+        self.triples = _check_triples(rotate.get("feature_indices") or [], self.F, "feature_indices", "x")
+        if not self.triples:
+            raise ValueError("rotate needs at least one column triple of x in feature_indices")
+        for s, e in self.triples:
+            if s <= k < e:
+                raise ValueError(f"node_type_index {k} lies inside the rotated columns ({s}, {e})")
+        ys, ye = self.y_columns
+        if ye - ys != 3:
+            raise ValueError(f"with rotate, y_columns ({ys}, {ye}) must be 3 wide: y is rotated as one 3D vector")
+        ea, ei = rotate.get("edge_attr"), rotate.get("edge_index")
+        if ea is None:
+            if ei is not None or rotate.get("edge_feature_indices") is not None:
+                raise ValueError("rotate: edge_index / edge_feature_indices are given without edge_attr")
+        else:
+            if not torch.is_tensor(ea) or ea.dtype != torch.float32 or ea.dim() != 2 or ea.device != dev or \
+                    not ea.is_contiguous():
+                raise ValueError(f"rotate edge_attr must be a contiguous fp32 [E, A] tensor on {dev}")
+            E, A = ea.shape
+            if not torch.is_tensor(ei) or ei.dim() != 2 or tuple(ei.shape) != (2, E) or ei.is_floating_point():
+                raise ValueError(f"rotate edge_index must be an integer [2, {E}] tensor (required with edge_attr)")
+            et = rotate.get("edge_feature_indices")
+            self.edge_triples = _check_triples([(0, 3)] if et is None else et, A, "edge_feature_indices", "edge_attr")
+            ei = ei.to(dev, torch.int64)
+            if E > 0 and (int(ei.min()) < 0 or int(ei.max()) >= self.N):
+                raise ValueError(f"rotate edge_index holds node ids outside [0, {self.N})")
+            node_graph = _node_graph(gp, self.N, dev)
+            g_src, g_dst = node_graph[ei[0]], node_graph[ei[1]]
+            if E > 0 and not torch.equal(g_src, g_dst):
+                bad = int(torch.nonzero(g_src != g_dst)[0])
+                raise ValueError(f"edge {bad} joins nodes of different graphs: one rotation per graph cannot rotate it")
+            self.edge_attr, self.row_graph = ea, g_src.to(torch.int32).contiguous()
+        self._triples_c, self._edge_triples_c = nat.feed_ranges(self.triples), nat.feed_ranges(self.edge_triples)
+        self.angles = torch.zeros(self.B, 3, dtype=torch.float32, device=dev)
+        self.R = torch.zeros(self.B, 9, dtype=torch.float32, device=dev)
+        self.random_rotations = True
+
+    def set_rotations(self, angles):
+        """"random" (the default of a feed with rotate=): every fill draws angles.uniform_(-π, π), one rotation
+        per graph. A host list / CPU tensor [B, 3] of radians {alpha (z), beta (y), gamma (x)}: the fills use
+        these until the next set_rotations. ValueError without rotate=, or for another shape."""
+        if self.angles is None:
+            raise ValueError("set_rotations: this feed was built without rotate=")
+        if isinstance(angles, str):
+            if angles != "random":
+                raise ValueError(f'angles must be "random" or [{self.B}, 3] radians, got {angles!r}')
+            self.random_rotations = True
+            return
+        a = torch.as_tensor(angles, dtype=torch.float32).cpu()
+        if tuple(a.shape) != (self.B, 3):
+            raise ValueError(f"expected three angles per graph, [{self.B}, 3], got {tuple(a.shape)}")
+        if not bool(torch.isfinite(a).all()):
+            raise ValueError("angles must be finite")
+        self.random_rotations = False
+        self.angles.copy_(a)
 
     def set_frames(self, frames):
         """"random": every fill draws its frames. A host list / CPU tensor of B frames, each in [0, T-2]
@@ -226,7 +367,10 @@ class ResidentTrajectories:
 
     def fill(self, batch):
         """Write batch.x[:, :F] and batch.y in place: device work only, capturable. HIP tensors: the frame /
-        noise draws and one mgn_feed_batch launch (no fallback); CPU tensors: fill_torch."""
+        noise draws and one mgn_feed_batch launch (no fallback); CPU tensors: fill_torch. With rotate=: the
+        angle draw, mgn_feed_rotation_matrices, one mgn_feed_batch_rot in mgn_feed_batch's place and, when a
+        clean edge_attr was given, one mgn_feed_rotate_rows into batch.edge_attr[:, :A]; CPU tensors: the
+        reference's matrix per graph, fill_torch and rotate_rows_torch."""
         x, y = batch.x, batch.y
         if x.device != self.traj.device or x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != self.N or \
                 x.shape[1] < self.F:
@@ -235,17 +379,45 @@ class ResidentTrajectories:
         wy = self.y_columns[1] - self.y_columns[0]
         if y is None or y.device != x.device or y.dtype != torch.float32 or tuple(y.shape) != (self.N, wy):
             raise ValueError(f"batch.y must be fp32 [{self.N}, {wy}] on {self.traj.device}")
+        rot = self.angles is not None
+        ea = None
+        if rot and self.edge_attr is not None:
+            ea, (E, A) = getattr(batch, "edge_attr", None), self.edge_attr.shape
+            if ea is None or ea.device != x.device or ea.dtype != torch.float32 or ea.dim() != 2 or \
+                    ea.shape[0] != E or ea.shape[1] < A or (ea.shape[1] > 1 and ea.stride(1) != 1):
+                raise ValueError(f"batch.edge_attr must be fp32 [{E}, >= {A}] on {self.traj.device}")
+            if E > 0 and ea.data_ptr() == self.edge_attr.data_ptr():
+                raise ValueError("batch.edge_attr is the feed's clean edge_attr: the fill would rotate it in place; "
+                                 "give the batch a copy")
         with torch.no_grad():
             if self.random_frames:
                 self.frame.random_(0, self.T - 1)  # torch.randint(0, T-1, (B,)) into the persistent tensor
             if self.z is not None:
                 self.z.normal_()
+            if rot and self.random_rotations:
+                self.angles.uniform_(-math.pi, math.pi)  # one rotation per graph, as the reference's per item
             if self.traj.is_cuda:
-                nat.feed_batch(self.traj, self.graph_ptr, self.frame, self.y_columns, self.node_type_index,
-                               self._ranges_c, self.scales, self.z, x, y)
+                if rot:
+                    nat.feed_rotation_matrices(self.angles, self.R)
+                    nat.feed_batch(self.traj, self.graph_ptr, self.frame, self.y_columns, self.node_type_index,
+                                   self._ranges_c, self.scales, self.z, x, y, self._triples_c, self.R)
+                    if ea is not None:
+                        nat.feed_rotate_rows(self.edge_attr, self.row_graph, self._edge_triples_c, self.R, ea)
+                else:
+                    nat.feed_batch(self.traj, self.graph_ptr, self.frame, self.y_columns, self.node_type_index,
+                                   self._ranges_c, self.scales, self.z, x, y)
             else:
+                if rot:
+                    from graphphysics.dataset.preprocessing import Random3DRotate
+
+                    build = Random3DRotate()._build_rotation_matrix
+                    if self.B:
+                        self.R.copy_(torch.stack([build(*a).reshape(9) for a in self.angles.tolist()]))
                 fx, fy = fill_torch(self.traj, self.graph_ptr, self.frame, self.y_columns, self.node_type_index,
-                                    self.ranges, self.scales, self.z)
+                                    self.ranges, self.scales, self.z, self.triples, self.R)
                 x[:, :self.F] = fx
                 y.copy_(fy)
+                if ea is not None:
+                    ea[:, :self.edge_attr.shape[1]] = rotate_rows_torch(self.edge_attr, self.row_graph,
+                                                                        self.edge_triples, self.R)
         return batch

@@ -40,7 +40,9 @@ per-graph frame draw, the noise draw and ONE libmgn launch that writes the batch
 device work of every step: recorded at the head of the captured step (ahead of the recorded statistics
 exchange), run eagerly before the statistics exchange where that exchange is eager. Each replay then trains
 on a new batch and the host still only writes {lr, step}. Switching the feed between drawn and explicit
-frames re-records the step (the draw is, or is not, part of the graph).
+frames re-records the step (the draw is, or is not, part of the graph). A feed built with rotate= also draws
+three angles per graph, builds the rotation matrices and rotates x, y and — into the step's private copy —
+edge_attr inside the same fill; switching set_rotations between drawn and explicit angles re-records as well.
 
 Validation errors flagged on libmgn's device error word (out-of-range edge_index, node types outside
 the one-hot range) surface as the reference's IndexError / RuntimeError at most one step late,
@@ -89,7 +91,7 @@ class TrainStep:
         # feed (dataset.resident.ResidentTrajectories): its fill(batch) is the first device work of every
         # step — recorded at the head of the captured step, so each replay trains on newly drawn frames and noise
         self.feed = feed
-        self._feed_random = None  # the feed's frame mode the graph was recorded in
+        self._feed_random = None  # the feed's (frame, rotation) draw modes the graph was recorded in
         self.masks = list(masks)
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
@@ -189,6 +191,10 @@ class TrainStep:
         for g, lr in zip(self.opt.param_groups, lrs):
             g["lr"] = lr
         sc._last_lr = list(lrs)
+
+    def _feed_mode(self):
+        """What the feed's fill draws: (frames drawn, angles drawn — None for a feed that does not rotate)."""
+        return (self.feed.random_frames, getattr(self.feed, "random_rotations", None))
 
     def eager(self):
         self._check_replicas()
@@ -348,7 +354,7 @@ class TrainStep:
                 # the batch itself is made inside the graph (frame and noise draws + one libmgn launch), ahead
                 # of the recorded statistics exchange: the statistics and the mask count see the fed batch
                 self.feed.fill(self.batch)
-                self._feed_random = self.feed.random_frames
+                self._feed_random = self._feed_mode()
             if self.overlap:
                 # RCCL: the statistics exchange (one statistics launch, the mask count, ONE all-reduce) is
                 # recorded too — it depends only on the batch the graph reads — so a step is ONE replay
@@ -396,8 +402,8 @@ class TrainStep:
             raise
         if self.graph is not None:
             self._sync_batch()
-            if self._feed_random is not None and self.feed.random_frames != self._feed_random:
-                self.graph = None  # the recorded fill draws (or does not draw) its frames: record it anew
+            if self._feed_random is not None and self._feed_mode() != self._feed_random:
+                self.graph = None  # the recorded fill draws (or does not draw) its frames / angles: record it anew
         if self._ctl is not None:
             # re-capture on every rank if any rank needs to (a rank that copies and
             # replays while another re-captures would pair mismatched collectives)

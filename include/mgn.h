@@ -543,6 +543,42 @@ int mgn_feed_batch(const float* traj, int64_t T, int64_t N, int32_t F,   /* [T, 
                    const float* z, int64_t ldz,            /* device standard normals [N, Σ(end-start)]; NULL: no noise */
                    float* x, int64_t ldx, float* y, int64_t ldy, mgn_stream_t stream);
 
+/* Rotation augmentation inside the feed (the reference's Random3DRotate, dataset/preprocessing.py:277-366): one
+ * rotation per graph, applied to column triples of a row as row vector times matrix, before the noise.
+ *   mgn_feed_rotation_matrices   R[g] (row-major 3x3) from angles[g] = {alpha (z), beta (y), gamma (x)} in
+ *                                radians, the reference's _build_rotation_matrix in fp32. One thread per graph.
+ *   mgn_feed_batch_rot           mgn_feed_batch, and for a column c of a triple (s, s + 3), with a = traj[t, r]:
+ *                                  x[r, c] = (a[s]*R[g][0][c-s] + a[s+1]*R[g][1][c-s]) + a[s+2]*R[g][2][c-s]
+ *                                then the noise rule of mgn_feed_batch on top of that value (the node type is read
+ *                                from the clean row). With n = traj[t + 1, r]:
+ *                                  y[r, j] = (n[y_start]*R[g][0][j] + n[y_start+1]*R[g][1][j]) + n[y_start+2]*R[g][2][j]
+ *                                Every product and every sum is rounded on its own, in that order, never an FMA:
+ *                                the same expression in torch's elementwise fp32 ops gives the same bits.
+ *                                triples.n == 0: exactly mgn_feed_batch (R is not read, y is a copy). One launch.
+ *   mgn_feed_rotate_rows         dst[r, c] = the same three-term rule on row r of src [rows, cols] with
+ *                                R[row_graph[r]] for a column of a triple, src[r, c] bit for bit for any other
+ *                                column and for every column of a row whose row_graph[r] is outside [0, B)
+ *                                (R is not read for it). For edge_attr. src and dst must not overlap. One launch.
+ * triples: `end` must equal `start + 3`. Before any launch, a nonzero status for a triple that is not 3 wide, a
+ * triple outside [0, F) ([0, cols) for _rotate_rows), overlapping triples, type_index inside a triple, triples
+ * with a y range that is neither empty nor 3 wide, triples with R == NULL, an ld smaller than its column count,
+ * overlapping src and dst, and everything mgn_feed_batch refuses. N == 0, B == 0 and rows == 0 return 0 without a
+ * launch. angles and R are read on the device at run time. No allocation, no synchronisation: capturable. The
+ * added symbols do not change MGN_ABI_VERSION; MGN_HAS_FEED_ROTATE marks headers that declare them. */
+#define MGN_HAS_FEED_ROTATE 1
+int mgn_feed_rotation_matrices(const float* angles /* device, [B, 3] */, int32_t B, float* R /* device, [B, 9] */,
+                               mgn_stream_t stream);
+int mgn_feed_batch_rot(const float* traj, int64_t T, int64_t N, int32_t F, const int32_t* graph_ptr, int32_t B,
+                       const int32_t* frame, int32_t y_start, int32_t y_end, int32_t type_index,
+                       mgn_feed_ranges ranges, const float* scales, const float* z, int64_t ldz,
+                       float* x, int64_t ldx, float* y, int64_t ldy,
+                       mgn_feed_ranges triples,                /* column triples of a frame row, end = start + 3 */
+                       const float* R,                         /* device, [B, 9]; may be NULL when triples.n == 0 */
+                       mgn_stream_t stream);
+int mgn_feed_rotate_rows(const float* src, int64_t rows, int32_t cols, int64_t ld_src,
+                         const int32_t* row_graph /* device, [rows] */, int32_t B, mgn_feed_ranges triples,
+                         const float* R /* device, [B, 9] */, float* dst, int64_t ld_dst, mgn_stream_t stream);
+
 /* Resident rollout: the data work of one autoregressive validation step (reference lightning_module.py:17-25,
  * 168-249) around the Simulator's evaluation forward, driven by a step counter on the device (*cursor, int32),
  * so a trajectory is S replays of one captured begin -> forward -> end. traj, graph_ptr and frame as in
