@@ -182,6 +182,159 @@ __global__ __launch_bounds__(256) void rotate_rows(const float* __restrict__ src
     dst[r * ld_dst + c] = v;
 }
 
+// ---- world positions (mgn.h, "World positions inside the feed"; reference add_obstacles_next_pos and
+// add_world_pos_features, dataset/preprocessing.py:49-89, 143-174) ----
+//
+// obstacle_mean: one workgroup per graph, so the sum needs no second pass, no workspace and no atomics. A
+// thread walks the graph's rows WORLD_MEAN_THREADS apart and adds the displacement n[j] - a[j] of its OBSTACLE
+// rows; the 64 lanes of a wave are summed by a shuffle tree, the wave sums by thread 0 in wave order: a fixed
+// order, so the same bits on every replay. A row costs two partly used cache lines here (a thread per row); the
+// kernel reads 2·rows·F floats in all, once per fill, and a DeformingPlate graph is about 1.4 k rows.
+constexpr int WORLD_MEAN_THREADS = 1024;
+
+__global__ __launch_bounds__(WORLD_MEAN_THREADS) void world_obstacle_mean(
+    const float* __restrict__ traj, int64_t N, int F, const int32_t* __restrict__ graph_ptr,
+    const int32_t* __restrict__ frame, int type_index, float* __restrict__ mean) {
+#pragma clang fp contract(off)
+    const int g = blockIdx.x;
+    const int64_t r0 = graph_ptr[g], r1 = graph_ptr[g + 1];
+    const float* cur = traj + (int64_t)frame[g] * N * F;
+    const float* nxt = cur + N * F;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    int m = 0;
+    for (int64_t r = r0 + threadIdx.x; r < r1; r += WORLD_MEAN_THREADS) {
+        const float* a = cur + r * F;
+        const float* n = nxt + r * F;
+        if (a[type_index] == 1.f) {  // NodeType.OBSTACLE
+            const float d0 = n[0] - a[0], d1 = n[1] - a[1], d2 = n[2] - a[2];
+            s0 = s0 + d0;
+            s1 = s1 + d1;
+            s2 = s2 + d2;
+            ++m;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {  // lane 0 ends with the wave's sum
+        s0 = s0 + __shfl_down(s0, off, 64);
+        s1 = s1 + __shfl_down(s1, off, 64);
+        s2 = s2 + __shfl_down(s2, off, 64);
+        m += __shfl_down(m, off, 64);
+    }
+    constexpr int WAVES = WORLD_MEAN_THREADS / 64;
+    __shared__ float ws[WAVES][3];
+    __shared__ int wm[WAVES];
+    if ((threadIdx.x & 63) == 0) {
+        const int w = threadIdx.x >> 6;
+        ws[w][0] = s0;
+        ws[w][1] = s1;
+        ws[w][2] = s2;
+        wm[w] = m;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t0 = ws[0][0], t1 = ws[0][1], t2 = ws[0][2];
+        int M = wm[0];
+        for (int w = 1; w < WAVES; ++w) {
+            t0 = t0 + ws[w][0];
+            t1 = t1 + ws[w][1];
+            t2 = t2 + ws[w][2];
+            M += wm[w];
+        }
+        // torch.mean's division by the count (correctly rounded: hipcc's default for fp32 division); a graph
+        // without an OBSTACLE row writes 0 where the reference's mean of nothing is NaN
+        const float cnt = (float)M;
+        mean[3 * (int64_t)g + 0] = M > 0 ? t0 / cnt : 0.f;
+        mean[3 * (int64_t)g + 1] = M > 0 ? t1 / cnt : 0.f;
+        mean[3 * (int64_t)g + 2] = M > 0 ? t2 / cnt : 0.f;
+    }
+}
+
+// feed_batch on the batch layout [world(3), displacement(3), the other F - 3 frame columns]: one thread per
+// element (r, c) of [N, F + 3], so x (when ldx == F + 3) is written as one contiguous span and the frame row is
+// read by consecutive lanes, as in feed_batch. y_start == 0 (checked on the host): the thread of column c < y_end
+// also copies column c of the next frame.
+__global__ __launch_bounds__(256) void feed_batch_world(const float* __restrict__ traj, int64_t N, int F,
+                                                        const int32_t* __restrict__ graph_ptr, int B,
+                                                        const int32_t* __restrict__ frame, int y_end,
+                                                        int type_index, mgn_feed_ranges rg,
+                                                        const float* __restrict__ scales,
+                                                        const float* __restrict__ z, int64_t ldz,
+                                                        float* __restrict__ x, int64_t ldx, float* __restrict__ y,
+                                                        int64_t ldy, const float* __restrict__ mean) {
+#pragma clang fp contract(off)  // x + z·s: a rounded product, then a rounded sum (see feed_batch)
+    const int Fx = F + 3;
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t total = N * Fx;
+    if (e >= total) return;
+    int64_t r;
+    if (total <= (int64_t)UINT32_MAX)
+        r = (uint32_t)e / (uint32_t)Fx;
+    else
+        r = e / Fx;
+    const int c = (int)(e - r * Fx);
+    const int g = graph_of_row(graph_ptr, B, r);
+    const int64_t t = frame[g];
+    const float* a = traj + (t * N + r) * F;
+    const float* n = a + (int64_t)N * F;
+    const float type = a[type_index];
+    float v;
+    if (c < 3)
+        v = a[c];
+    else if (c < 6)
+        v = type == 1.f ? n[c - 3] - a[c - 3] : mean[3 * (int64_t)g + (c - 3)];
+    else
+        v = a[c - 3];
+    if (z != nullptr) {
+        int zc = -1, which = 0, w = 0;
+#pragma unroll
+        for (int i = 0; i < MGN_FEED_MAX_RANGES; ++i)
+            if (i < rg.n) {
+                if (c >= rg.start[i] && c < rg.end[i]) {
+                    zc = w + c - rg.start[i];
+                    which = i;
+                }
+                w += rg.end[i] - rg.start[i];
+            }
+        if (zc >= 0 && type == 0.f) {
+            const float noise = z[r * ldz + zc] * scales[which];
+            v = v + noise;
+        }
+    }
+    x[r * ldx + c] = v;
+    if (c < y_end) y[r * ldy + c] = n[c];
+}
+
+// One thread per edge: the two gathered world positions of the (noisy) batch rows, their difference and its
+// norm, (v0·v0 + v1·v1) + v2·v2 with every product and sum rounded on its own and a correctly rounded square
+// root (hipcc's default for fp32 sqrtf). VEC: the four values leave as one 16-byte store (an instantiation of its
+// own: as a run-time branch the compiler merged both paths into a 12-byte and a 4-byte store).
+template <bool VEC>
+__global__ __launch_bounds__(256) void world_edge_features(const int32_t* __restrict__ senders,
+                                                           const int32_t* __restrict__ receivers, int64_t E,
+                                                           const float* __restrict__ x, int64_t ldx,
+                                                           float* __restrict__ edge_attr, int64_t ld_ea, int s) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= E) return;
+    const float* p = x + (int64_t)senders[e] * ldx;
+    const float* q = x + (int64_t)receivers[e] * ldx;
+    const float v0 = p[0] - q[0], v1 = p[1] - q[1], v2 = p[2] - q[2];
+    const float q0 = v0 * v0;
+    const float q1 = v1 * v1;
+    const float q2 = v2 * v2;
+    const float s01 = q0 + q1;
+    const float d = sqrtf(s01 + q2);
+    float* o = edge_attr + e * ld_ea + s;
+    if (VEC) {
+        *reinterpret_cast<float4*>(o) = make_float4(v0, v1, v2, d);
+    } else {
+        o[0] = v0;
+        o[1] = v1;
+        o[2] = v2;
+        o[3] = d;
+    }
+}
+
 // The host-side checks of column triples against a row of `width` columns; 0 or the status of MGN_REQUIRE.
 int check_triples(const std::string& who, const mgn_feed_ranges& tr, int64_t width, const char* width_name) {
     MGN_REQUIRE(tr.n >= 0 && tr.n <= MGN_FEED_MAX_RANGES, who + ": at most 4 column triples");
@@ -195,10 +348,12 @@ int check_triples(const std::string& who, const mgn_feed_ranges& tr, int64_t wid
     return 0;
 }
 
-// Every argument check mgn_feed_batch makes ahead of its N == 0 return; *W: the noisy column count.
+// Every argument check mgn_feed_batch makes ahead of its N == 0 return; *W: the noisy column count. Fx: the
+// width of a batch row, which the noisy ranges and ldx are checked against (F, or F + 3 for feed_batch_world).
 int check_feed(const std::string& who, int64_t T, int64_t N, int32_t F, int32_t B, int32_t y_start, int32_t y_end,
                int32_t type_index, const mgn_feed_ranges& ranges, const float* z, int64_t ldz, int64_t ldx,
-               int64_t ldy, int64_t* W_out) {
+               int64_t ldy, int64_t* W_out, int32_t Fx) {
+    const std::string width = Fx == F ? "F" : "F + 3";
     MGN_REQUIRE(T >= 2, who + ": a trajectory needs at least 2 frames (x from frame t, y from t + 1)");
     MGN_REQUIRE(F >= 1, who + ": F must be >= 1");
     MGN_REQUIRE(N >= 0 && B >= 0, who + ": N and B must be >= 0");
@@ -206,8 +361,8 @@ int check_feed(const std::string& who, int64_t T, int64_t N, int32_t F, int32_t 
     MGN_REQUIRE(ranges.n >= 0 && ranges.n <= MGN_FEED_MAX_RANGES, who + ": at most 4 noisy column ranges");
     int64_t W = 0;
     for (int i = 0; i < ranges.n; ++i) {
-        MGN_REQUIRE(ranges.start[i] >= 0 && ranges.start[i] <= ranges.end[i] && ranges.end[i] <= F,
-                    who + ": a noisy column range is outside [0, F]");
+        MGN_REQUIRE(ranges.start[i] >= 0 && ranges.start[i] <= ranges.end[i] && ranges.end[i] <= Fx,
+                    who + ": a noisy column range is outside [0, " + width + "]");
         for (int j = 0; j < i; ++j)
             MGN_REQUIRE(ranges.start[i] >= ranges.end[j] || ranges.start[j] >= ranges.end[i] ||
                             ranges.start[i] == ranges.end[i] || ranges.start[j] == ranges.end[j],
@@ -216,7 +371,7 @@ int check_feed(const std::string& who, int64_t T, int64_t N, int32_t F, int32_t 
     }
     MGN_REQUIRE(y_start >= 0 && y_start <= y_end && y_end <= F, who + ": the y column range is outside [0, F]");
     MGN_REQUIRE(type_index >= 0 && type_index < F, who + ": type_index is outside [0, F)");
-    MGN_REQUIRE(ldx >= F, who + ": ldx is smaller than F");
+    MGN_REQUIRE(ldx >= Fx, who + ": ldx is smaller than " + width);
     MGN_REQUIRE(ldy >= y_end - y_start, who + ": ldy is smaller than the y column count");
     MGN_REQUIRE(z == nullptr || ldz >= W, who + ": ldz is smaller than the noisy column count");
     *W_out = W;
@@ -232,7 +387,7 @@ int mgn_feed_batch(const float* traj, int64_t T, int64_t N, int32_t F, const int
                    const float* scales, const float* z, int64_t ldz, float* x, int64_t ldx, float* y, int64_t ldy,
                    mgn_stream_t stream) {
     int64_t W = 0;
-    if (int rc = check_feed("feed_batch", T, N, F, B, y_start, y_end, type_index, ranges, z, ldz, ldx, ldy, &W))
+    if (int rc = check_feed("feed_batch", T, N, F, B, y_start, y_end, type_index, ranges, z, ldz, ldx, ldy, &W, F))
         return rc;
     if (N == 0 || B == 0) return 0;
     MGN_REQUIRE(traj && graph_ptr && frame && x && (y || y_start == y_end), "feed_batch: a null pointer argument");
@@ -261,7 +416,7 @@ int mgn_feed_batch_rot(const float* traj, int64_t T, int64_t N, int32_t F, const
                        mgn_feed_ranges ranges, const float* scales, const float* z, int64_t ldz, float* x, int64_t ldx,
                        float* y, int64_t ldy, mgn_feed_ranges triples, const float* R, mgn_stream_t stream) {
     int64_t W = 0;
-    if (int rc = check_feed("feed_batch_rot", T, N, F, B, y_start, y_end, type_index, ranges, z, ldz, ldx, ldy, &W))
+    if (int rc = check_feed("feed_batch_rot", T, N, F, B, y_start, y_end, type_index, ranges, z, ldz, ldx, ldy, &W, F))
         return rc;
     if (int rc = check_triples("feed_batch_rot", triples, F, "F")) return rc;
     for (int i = 0; i < triples.n; ++i)
@@ -307,6 +462,59 @@ int mgn_feed_rotate_rows(const float* src, int64_t rows, int32_t cols, int64_t l
     MGN_REQUIRE(blocks <= INT32_MAX, "feed_rotate_rows: rows * cols is too large for one launch");
     hipLaunchKernelGGL(rotate_rows, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, rows, (int)cols,
                        ld_src, row_graph, (int)B, triples, R, dst, ld_dst);
+    MGN_LAUNCH_CHECK();
+    return 0;
+}
+
+int mgn_feed_batch_world(const float* traj, int64_t T, int64_t N, int32_t F, const int32_t* graph_ptr, int32_t B,
+                         const int32_t* frame, int32_t y_start, int32_t y_end, int32_t type_index,
+                         mgn_feed_ranges ranges, const float* scales, const float* z, int64_t ldz, float* x,
+                         int64_t ldx, float* y, int64_t ldy, float* obstacle_mean, mgn_stream_t stream) {
+    const std::string who = "feed_batch_world";
+    MGN_REQUIRE(F >= 4 && F <= INT32_MAX - 3, who + ": F must be >= 4 (world position and a node type)");
+    int64_t W = 0;
+    if (int rc = check_feed(who, T, N, F, B, y_start, y_end, type_index, ranges, z, ldz, ldx, ldy, &W, F + 3)) return rc;
+    MGN_REQUIRE(type_index >= 3, who + ": type_index lies inside the world position columns [0, 3)");
+    MGN_REQUIRE(y_start == 0 && y_end >= 3, who + ": the y columns must begin with the world position "
+                                                  "(y_start == 0, y_end >= 3)");
+    for (int i = 0; i < ranges.n; ++i)
+        MGN_REQUIRE(ranges.start[i] == ranges.end[i] || type_index + 3 < ranges.start[i] ||
+                        type_index + 3 >= ranges.end[i],
+                    who + ": a noisy column range contains the node type (batch column type_index + 3)");
+    MGN_REQUIRE(obstacle_mean != nullptr, who + ": obstacle_mean is null");
+    if (N == 0 || B == 0) return 0;
+    MGN_REQUIRE(traj && graph_ptr && frame && x && y, who + ": a null pointer argument");
+    MGN_REQUIRE(z == nullptr || W == 0 || scales != nullptr, who + ": noise (z) without scales");
+    const int64_t blocks = cdiv64(N * (F + 3), 256);
+    MGN_REQUIRE(blocks <= INT32_MAX, who + ": N * (F + 3) is too large for one launch");
+    hipLaunchKernelGGL(world_obstacle_mean, dim3((unsigned)B), dim3(WORLD_MEAN_THREADS), 0, (hipStream_t)stream, traj,
+                       N, (int)F, graph_ptr, frame, (int)type_index, obstacle_mean);
+    MGN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(feed_batch_world, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, traj, N, (int)F,
+                       graph_ptr, (int)B, frame, (int)y_end, (int)type_index, ranges, scales, W > 0 ? z : nullptr,
+                       ldz, x, ldx, y, ldy, obstacle_mean);
+    MGN_LAUNCH_CHECK();
+    return 0;
+}
+
+int mgn_feed_world_edge_features(const int32_t* senders, const int32_t* receivers, int64_t E, const float* x,
+                                 int64_t ldx, float* edge_attr, int64_t ld_ea, int32_t start, mgn_stream_t stream) {
+    const std::string who = "feed_world_edge_features";
+    MGN_REQUIRE(E >= 0, who + ": E must be >= 0");
+    MGN_REQUIRE(start >= 0, who + ": the start column must be >= 0");
+    MGN_REQUIRE(ld_ea >= (int64_t)start + 4, who + ": ld_ea is smaller than start + 4");
+    MGN_REQUIRE(ldx >= 3, who + ": ldx is smaller than 3");
+    if (E == 0) return 0;
+    MGN_REQUIRE(senders && receivers && x && edge_attr, who + ": a null pointer argument");
+    const int64_t blocks = cdiv64(E, 256);
+    MGN_REQUIRE(blocks <= INT32_MAX, who + ": E is too large for one launch");
+    const bool vec = start % 4 == 0 && ld_ea % 4 == 0 && reinterpret_cast<uintptr_t>(edge_attr) % 16 == 0;
+    if (vec)
+        hipLaunchKernelGGL(world_edge_features<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                           senders, receivers, E, x, ldx, edge_attr, ld_ea, (int)start);
+    else
+        hipLaunchKernelGGL(world_edge_features<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                           senders, receivers, E, x, ldx, edge_attr, ld_ea, (int)start);
     MGN_LAUNCH_CHECK();
     return 0;
 }

@@ -186,6 +186,9 @@ EXPORTS = {
     "mgn_feed_batch_rot": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _i32, FeedRanges, _vp, _vp,
                                   _i64, _vp, _i64, _vp, _i64, FeedRanges, _vp, _vp]),
     "mgn_feed_rotate_rows": (_i32, [_vp, _i64, _i32, _i64, _vp, _i32, FeedRanges, _vp, _vp, _i64, _vp]),
+    "mgn_feed_batch_world": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _i32, FeedRanges, _vp, _vp,
+                                    _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "mgn_feed_world_edge_features": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp]),
     "mgn_rollout_begin": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
                                  _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "mgn_rollout_end_workspace_bytes": (_sz, [_i64]),
@@ -580,6 +583,60 @@ def feed_rotate_rows(src, row_graph, triples, R, dst):
     tr = triples if isinstance(triples, FeedRanges) else feed_ranges(triples)
     check(lib().mgn_feed_rotate_rows(ptr(src), rows, cols, src.stride(0), ptr(row_graph), R.shape[0], tr, ptr(R),
                                      ptr(dst), dst.stride(0), stream_ptr(src.device)))
+
+
+def feed_batch_world(traj, graph_ptr, frame, y_columns, type_index, ranges, scales, z, x, y, obstacle_mean):
+    """One Lagrangian training batch from resident trajectories (mgn_feed_batch_world): x[:, :F + 3] =
+    [world(3), obstacle displacement(3), the other columns] of frame[g] of traj [T, N, F], y = y_columns of the
+    next clean frame, obstacle_mean [B, 3] = the per-graph mean displacement of the OBSTACLE rows. type_index is
+    the node-type column of a frame row; ranges are noisy columns of the batch row. Writes x, y and obstacle_mean
+    in place on the current stream."""
+    import torch
+
+    require_device(traj)
+    if traj.dtype != torch.float32 or traj.dim() != 3 or not traj.is_contiguous():
+        raise ValueError("feed_batch_world: traj must be a contiguous fp32 [T, N, F] tensor")
+    T, N, F = traj.shape
+    for name, t, rows in (("x", x, N), ("y", y, N), ("z", z, N)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != rows or
+                              (t.shape[1] > 1 and t.stride(1) != 1) or t.device != traj.device):
+            raise ValueError(f"feed_batch_world: {name} must be an fp32 [{rows}, cols] tensor on traj's device with "
+                             "unit column stride")
+    if graph_ptr.dtype != torch.int32 or frame.dtype != torch.int32 or graph_ptr.numel() != frame.numel() + 1:
+        raise ValueError("feed_batch_world: graph_ptr [B+1] and frame [B] must be int32 tensors")
+    if x.shape[1] < F + 3 or y.shape[1] != y_columns[1] - y_columns[0]:
+        raise ValueError("feed_batch_world: x needs at least F + 3 columns and y exactly y_columns[1] - y_columns[0]")
+    m = obstacle_mean
+    if m.dtype != torch.float32 or tuple(m.shape) != (frame.numel(), 3) or not m.is_contiguous() or \
+            m.device != traj.device:
+        raise ValueError(f"feed_batch_world: obstacle_mean must be a contiguous fp32 [{frame.numel()}, 3] tensor on "
+                         "traj's device")
+    rg = ranges if isinstance(ranges, FeedRanges) else feed_ranges(ranges)
+    check(lib().mgn_feed_batch_world(ptr(traj), T, N, F, ptr(graph_ptr), frame.numel(), ptr(frame), int(y_columns[0]),
+                                     int(y_columns[1]), int(type_index), rg, ptr(scales), ptr(z),
+                                     z.stride(0) if z is not None else 0, ptr(x), x.stride(0), ptr(y), y.stride(0),
+                                     ptr(m), stream_ptr(traj.device)))
+
+
+def feed_world_edge_features(senders, receivers, x, edge_attr, start):
+    """edge_attr[:, start:start + 4] = [x[senders, 0:3] - x[receivers, 0:3] ‖ its norm]
+    (mgn_feed_world_edge_features); other columns of edge_attr are not touched. senders / receivers: contiguous
+    int32 [E] with node ids inside [0, rows of x) — the caller's precondition, not checked here. On the current
+    stream."""
+    import torch
+
+    require_device(x)
+    E = senders.numel()
+    for name, t in (("senders", senders), ("receivers", receivers)):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != E or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"feed_world_edge_features: {name} must be a contiguous int32 [{E}] tensor on x's device")
+    for name, t, rows, cols in (("x", x, x.shape[0], 3), ("edge_attr", edge_attr, E, int(start) + 4)):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < cols or \
+                t.stride(1) != 1 or t.device != x.device:
+            raise ValueError(f"feed_world_edge_features: {name} must be an fp32 [{rows}, >= {cols}] tensor on x's "
+                             "device with unit column stride")
+    check(lib().mgn_feed_world_edge_features(ptr(senders), ptr(receivers), E, ptr(x), x.stride(0), ptr(edge_attr),
+                                             edge_attr.stride(0), int(start), stream_ptr(x.device)))
 
 
 def _rollout_2d(fn, name, t, rows, dev, cols=None):

@@ -18,9 +18,20 @@ the column triples of x and the 3 columns of y rotated by the fill's own launch 
 (mgn_feed_rotate_rows). The rule is row vector times matrix written term by term, (a0·R0j + a1·R1j) + a2·R2j,
 so the torch ops of fill_torch / rotate_rows_torch give the kernels' bits.
 
-Not supported: `previous_data`, per-frame positions or edge_attr (Lagrangian datasets), and trajectories of
+World positions (world_pos=; Lagrangian data such as DeformingPlate, the reference's world_pos_parameters
+stages add_obstacles_next_pos and add_world_pos_features, dataset/preprocessing.py:49-89 and 143-174, in
+build_preprocessing's order): the batch row is [world(3), obstacle displacement(3), the other frame columns] —
+the displacement of a row's own next clean position for OBSTACLE rows, the per-graph mean of those (a fixed-order
+fp32 sum divided by the count) for the others — written by mgn_feed_batch_world (a reduction per graph, then the
+fill) with the noise on top, in batch-layout columns; then, when the feed was given an edge_index,
+mgn_feed_world_edge_features writes the relative world positions of the noisy x and their norm into four
+columns of batch.edge_attr. fill_world_torch / world_edge_features_torch state both rules term by term.
+
+Not supported: `previous_data`, world edges that change from frame to frame (the edge_index given with
+world_pos= is static for the life of the feed: the radius search is not part of the fill), the Lagrangian
+rollout (Rollout refuses a feed built with world_pos=), rotate= together with world_pos=, and trajectories of
 unequal length in one batch. batch.edge_index is never touched, batch.edge_attr only by a rotating feed that
-was given a clean edge_attr.
+was given a clean edge_attr and by a world_pos= feed that was given an edge_index.
 
 The validation rollout reads the same resident frames (training.rollout.Rollout.rollout_resident):
 rollout_begin_torch / rollout_end_torch state, as torch ops on any device, the two rules libmgn's
@@ -145,6 +156,57 @@ def fill_torch(traj, graph_ptr, frame, y_columns, node_type_index, ranges, scale
     return x, y
 
 
+def fill_world_torch(traj, graph_ptr, frame, y_columns, node_type_index, ranges, scales, z):
+    """mgn_feed_batch_world's rule as torch ops on any device: returns (x [N, F + 3], y [N, y_end - y_start],
+    obstacle_mean [B, 3]) as new tensors. With a = frame[g] of traj and n the next frame: disp = n[:, 0:3] −
+    a[:, 0:3] from clean values; obstacle_mean[g] = the sum of disp over the OBSTACLE rows of g divided by their
+    count M (0 for M = 0), written sum(0) / M — a division, as torch.mean on the CPU, by a tensor: a GPU division
+    by a host scalar multiplies by the reciprocal —; x = [a[:, 0:3], disp on OBSTACLE rows and obstacle_mean[g]
+    on the others, a[:, 3:]]; then fill_torch's noise with `ranges` in the columns of this batch layout and the
+    node type read from the clean frame column node_type_index; y = the y_columns of n. What
+    ResidentTrajectories(world_pos=...).fill runs on CPU tensors, and what the kernels are tested against."""
+    T, N, F = traj.shape
+    dev = traj.device
+    gp = [int(v) for v in (graph_ptr.tolist() if torch.is_tensor(graph_ptr) else graph_ptr)]
+    rows = torch.arange(N, device=dev)
+    node_graph = _node_graph(gp, N, dev)
+    t = frame.to(dev, torch.int64)[node_graph]
+    a, n = traj[t, rows], traj[t + 1, rows]
+    y = n[:, y_columns[0]:y_columns[1]].contiguous()
+    disp = n[:, 0:3] - a[:, 0:3]
+    obstacle = a[:, node_type_index] == NodeType.OBSTACLE
+    mean = torch.zeros(len(gp) - 1, 3, dtype=torch.float32, device=dev)
+    for g in range(len(gp) - 1):
+        d = disp[gp[g]:gp[g + 1]][obstacle[gp[g]:gp[g + 1]]]
+        if d.shape[0] > 0:
+            mean[g] = d.sum(0) / torch.full((), d.shape[0], dtype=torch.float32, device=dev)
+    x = torch.cat([a[:, 0:3], torch.where(obstacle[:, None], disp, mean[node_graph]), a[:, 3:]], dim=1)
+    if z is not None:
+        normal = (a[:, node_type_index] == NodeType.NORMAL)[:, None]
+        zc = 0
+        for i, (s, e) in enumerate(ranges):
+            feature = x[:, s:e]
+            noise = z[:, zc:zc + e - s] * scales[i]
+            x[:, s:e] = torch.where(normal, feature + noise, feature)
+            zc += e - s
+    return x, y, mean
+
+
+def world_edge_features_torch(x, edge_index, edge_attr, start):
+    """mgn_feed_world_edge_features' rule as torch ops on any device, in place on edge_attr [E, >= start + 4]:
+    v = x[senders, 0:3] − x[receivers, 0:3] (senders = edge_index[0]) into columns [start, start + 3) and
+    sqrt((v0·v0 + v1·v1) + v2·v2), term by term, into column start + 3; other columns are not touched. The
+    kernel's square root is correctly rounded; torch.sqrt in fp32 does not promise that (on the CPU, a contiguous
+    tensor goes through a vector library that is accurate to 1 ulp only), so the root of the fp32 sum is taken in
+    fp64 and rounded to fp32: 53 bits are more than the 2·24 + 2 that make this double rounding exact."""
+    ei = edge_index.to(x.device, torch.int64)
+    v = x[ei[0], 0:3] - x[ei[1], 0:3]
+    edge_attr[:, start:start + 3] = v
+    sumsq = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
+    edge_attr[:, start + 3] = torch.sqrt(sumsq.double()).float()
+    return edge_attr
+
+
 def check_rollout_columns(F, y_columns, out_columns, prev_columns, node_type_index):
     """The host-side preconditions of a resident rollout (ValueError): the model's output columns, the target
     columns and, when used, the previous-data columns have one width d; the output and previous-data ranges
@@ -225,8 +287,8 @@ class ResidentTrajectories:
 
     frame [B] int32, z [N, W] fp32 (None without noise) and scales [n] fp32 (None without noise) are
     allocated once and only rewritten: a captured graph keeps reading the same addresses, tests and users
-    read there what the last fill used. Not supported: previous_data, per-frame positions or edge_attr,
-    trajectories of unequal length (module docstring).
+    read there what the last fill used. Not supported: previous_data, per-frame world edges, the Lagrangian
+    rollout, trajectories of unequal length (module docstring).
 
     rotate: None, or the rotation augmentation of the reference's Random3DRotate, one rotation per graph and
     fill, as a dict
@@ -238,11 +300,27 @@ class ResidentTrajectories:
     gamma about x) and R [B, 9] (row-major 3x3 per graph) are persistent like frame and z; row_graph [E] int32
     is the graph of every edge, built once. fill writes the rotated edge_attr into batch.edge_attr[:, :A]; the
     clean edge_attr, like traj, is only read. batch.pos is not touched (no model here reads it in the step).
-    See set_rotations."""
+    See set_rotations.
+
+    world_pos: None, or the reference's world_pos_parameters (Lagrangian data such as DeformingPlate: world
+    position in frame columns [0, 3)) plus the edge side, as a dict
+      {"world_pos_index_start": 0, "world_pos_index_end": 3,   # the reference hard-codes the width 3
+       "node_type_index": node_type_index + 3,                 # batch layout, as the config writes it
+       "edge_index": edge_index,                               # optional: [2, E], static for the life of the feed
+       "edge_attr_start": 4}                                   # required with edge_index: first written column
+    The batch row is then F + 3 wide, [world(3), obstacle displacement(3), the other frame columns], so the
+    node type of frame column node_type_index sits in batch column node_type_index + 3; noise's indices and its
+    node_type_index are in that batch layout too. y_columns must begin with the world position (start 0, end
+    >= 3). Every graph needs an OBSTACLE node: checked on frame 0, node types are assumed constant over the
+    frames. obstacle_mean [B, 3] is persistent like frame and z; senders / receivers [E] int32 are built once.
+    With an edge side fill writes batch.edge_attr[:, edge_attr_start : edge_attr_start + 4] from the noisy x and
+    touches no other column (the mesh's Cartesian ‖ Distance columns stay). Not together with rotate=."""
 
     ROTATE_KEYS = ("feature_indices", "edge_attr", "edge_index", "edge_feature_indices")
+    WORLD_KEYS = ("world_pos_index_start", "world_pos_index_end", "node_type_index", "edge_index", "edge_attr_start")
 
-    def __init__(self, traj, graph_ptr, y_columns, node_type_index, noise=None, frames="random", rotate=None):
+    def __init__(self, traj, graph_ptr, y_columns, node_type_index, noise=None, frames="random", rotate=None,
+                 world_pos=None):
         if not torch.is_tensor(traj) or traj.dtype != torch.float32 or traj.dim() != 3 or not traj.is_contiguous():
             raise ValueError("traj must be a contiguous fp32 [T, N, F] tensor")
         T, N, F = traj.shape
@@ -261,13 +339,25 @@ class ResidentTrajectories:
         dev = traj.device
         self.graph_ptr = torch.tensor(gp, dtype=torch.int32, device=dev)
         self.ranges, self._base_scales, self.scales, self.z = [], [], None, None
+        # world_pos=: the batch row is [world(3), displacement(3), the other columns], 3 wider than a frame row
+        self.world = world_pos is not None
+        self.obstacle_mean, self.senders, self.receivers, self.edge_attr_start = None, None, None, None
+        if self.world:
+            if rotate is not None:
+                raise ValueError("rotate= together with world_pos= is not supported")
+            self._init_world(world_pos, gp)
+        self.Fx = F + 3 if self.world else F  # the width of a batch row
+        type_column = self.node_type_index + 3 if self.world else self.node_type_index
         if noise is not None:
-            if int(noise["node_type_index"]) != self.node_type_index:
+            if int(noise["node_type_index"]) != type_column:
                 raise ValueError(f"noise node_type_index {noise['node_type_index']} differs from node_type_index "
-                                 f"{self.node_type_index}")
+                                 f"{type_column}" + (" (batch layout: the frame's node_type_index + 3)"
+                                                     if self.world else ""))
             start, end, self._base_scales = _noise_lists(noise)
             self.ranges = list(zip(start, end))
-            _check_ranges(self.ranges, F)
+            _check_ranges(self.ranges, self.Fx)
+            if self.world and any(s <= type_column < e for s, e in self.ranges):
+                raise ValueError(f"a noisy column range contains the node type (batch column {type_column})")
             width = sum(e - s for s, e in self.ranges)
             if width > 0:
                 self.scales = torch.tensor(self._base_scales, dtype=torch.float32, device=dev)
@@ -281,6 +371,48 @@ class ResidentTrajectories:
         self.random_rotations = None  # None: no rotation; True: drawn on every fill; False: explicit angles
         if rotate is not None:
             self._init_rotate(rotate, gp)
+
+    def _init_world(self, wp, gp):
+        if not isinstance(wp, dict) or any(k not in self.WORLD_KEYS for k in wp):
+            raise ValueError(f"world_pos must be a dict with keys among {self.WORLD_KEYS}, got {wp!r}")
+        dev, k, F, N = self.traj.device, self.node_type_index, self.F, self.N
+        try:
+            ws, we, nti = (int(wp[key]) for key in self.WORLD_KEYS[:3])
+        except KeyError as ex:
+            raise ValueError(f"world_pos needs {ex.args[0]}") from None
+        if ws != 0 or we - ws != 3:
+            raise ValueError(f"world_pos columns ({ws}, {we}) must be (0, 3): the reference's displacement is 3 wide "
+                             "and the columns ahead of the world position are dropped")
+        if F < 4 or k < 3:
+            raise ValueError(f"world_pos needs frame rows [world(3), ..., node type, ...]: F = {F} >= 4 and "
+                             f"node_type_index = {k} >= 3")
+        if nti != k + 3:
+            raise ValueError(f"world_pos node_type_index {nti} differs from node_type_index + 3 = {k + 3} (the batch "
+                             "layout, after the 3 displacement columns are inserted)")
+        ys, ye = self.y_columns
+        if ys != 0 or ye < 3:
+            raise ValueError(f"with world_pos, y_columns ({ys}, {ye}) must begin with the world position: start 0, "
+                             "end >= 3")
+        obstacle = self.traj[0, :, k] == NodeType.OBSTACLE
+        for g in range(self.B):
+            if not bool(obstacle[gp[g]:gp[g + 1]].any()):
+                raise ValueError(f"graph {g} has no OBSTACLE node in frame 0: its mean obstacle displacement is "
+                                 "undefined (NaN in the reference)")
+        ei, start = wp.get("edge_index"), wp.get("edge_attr_start")
+        if (ei is None) != (start is None):
+            raise ValueError("world_pos: edge_index and edge_attr_start go together")
+        if ei is not None:
+            if not torch.is_tensor(ei) or ei.dim() != 2 or ei.shape[0] != 2 or ei.is_floating_point() or \
+                    ei.dtype == torch.bool:
+                raise ValueError("world_pos edge_index must be an integer [2, E] tensor")
+            if int(start) < 0:
+                raise ValueError(f"world_pos edge_attr_start {start} must be >= 0")
+            ei = ei.to(dev, torch.int64)
+            if ei.shape[1] > 0 and (int(ei.min()) < 0 or int(ei.max()) >= N):
+                raise ValueError(f"world_pos edge_index holds node ids outside [0, {N})")
+            self.senders, self.receivers = ei[0].to(torch.int32).contiguous(), ei[1].to(torch.int32).contiguous()
+            self.edge_attr_start, self._world_edge_index = int(start), ei
+        self.obstacle_mean = torch.zeros(self.B, 3, dtype=torch.float32, device=dev)
 
     def _init_rotate(self, rotate, gp):
         if not isinstance(rotate, dict) or any(k not in self.ROTATE_KEYS for k in rotate):
@@ -370,11 +502,14 @@ class ResidentTrajectories:
         noise draws and one mgn_feed_batch launch (no fallback); CPU tensors: fill_torch. With rotate=: the
         angle draw, mgn_feed_rotation_matrices, one mgn_feed_batch_rot in mgn_feed_batch's place and, when a
         clean edge_attr was given, one mgn_feed_rotate_rows into batch.edge_attr[:, :A]; CPU tensors: the
-        reference's matrix per graph, fill_torch and rotate_rows_torch."""
+        reference's matrix per graph, fill_torch and rotate_rows_torch. With world_pos=: batch.x[:, :F + 3], one
+        mgn_feed_batch_world (two launches) in mgn_feed_batch's place and, with an edge side, one
+        mgn_feed_world_edge_features into batch.edge_attr[:, start:start + 4]; CPU tensors: fill_world_torch and
+        world_edge_features_torch."""
         x, y = batch.x, batch.y
         if x.device != self.traj.device or x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != self.N or \
-                x.shape[1] < self.F:
-            raise ValueError(f"batch.x must be fp32 [{self.N}, >= {self.F}] on {self.traj.device}, got "
+                x.shape[1] < self.Fx:
+            raise ValueError(f"batch.x must be fp32 [{self.N}, >= {self.Fx}] on {self.traj.device}, got "
                              f"{tuple(x.shape)} {x.dtype} on {x.device}")
         wy = self.y_columns[1] - self.y_columns[0]
         if y is None or y.device != x.device or y.dtype != torch.float32 or tuple(y.shape) != (self.N, wy):
@@ -389,11 +524,33 @@ class ResidentTrajectories:
             if E > 0 and ea.data_ptr() == self.edge_attr.data_ptr():
                 raise ValueError("batch.edge_attr is the feed's clean edge_attr: the fill would rotate it in place; "
                                  "give the batch a copy")
+        wea = None
+        if self.senders is not None:
+            wea, E, A = getattr(batch, "edge_attr", None), self.senders.numel(), self.edge_attr_start + 4
+            if wea is None or wea.device != x.device or wea.dtype != torch.float32 or wea.dim() != 2 or \
+                    wea.shape[0] != E or wea.shape[1] < A or wea.stride(1) != 1:
+                raise ValueError(f"batch.edge_attr must be fp32 [{E}, >= {A}] on {self.traj.device} with unit column "
+                                 "stride")
         with torch.no_grad():
             if self.random_frames:
                 self.frame.random_(0, self.T - 1)  # torch.randint(0, T-1, (B,)) into the persistent tensor
             if self.z is not None:
                 self.z.normal_()
+            if self.world:
+                if self.traj.is_cuda:
+                    nat.feed_batch_world(self.traj, self.graph_ptr, self.frame, self.y_columns, self.node_type_index,
+                                         self._ranges_c, self.scales, self.z, x, y, self.obstacle_mean)
+                    if wea is not None:
+                        nat.feed_world_edge_features(self.senders, self.receivers, x, wea, self.edge_attr_start)
+                else:
+                    fx, fy, mean = fill_world_torch(self.traj, self.graph_ptr, self.frame, self.y_columns,
+                                                    self.node_type_index, self.ranges, self.scales, self.z)
+                    x[:, :self.Fx] = fx
+                    y.copy_(fy)
+                    self.obstacle_mean.copy_(mean)
+                    if wea is not None:
+                        world_edge_features_torch(x, self._world_edge_index, wea, self.edge_attr_start)
+                return batch
             if rot and self.random_rotations:
                 self.angles.uniform_(-math.pi, math.pi)  # one rotation per graph, as the reference's per item
             if self.traj.is_cuda:

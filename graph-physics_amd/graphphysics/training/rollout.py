@@ -75,11 +75,21 @@ class Rollout:
         if feed is not None:
             from graphphysics.dataset.resident import check_rollout_columns
 
+            self._refuse_world(feed)
             if torch.device(sim.device).type != feed.traj.device.type:
                 raise ValueError(f"feed lives on {feed.traj.device}, the simulator on {sim.device}")
             self._prev_cols = (int(self.ps), int(self.pe)) if self.use_prev else None
             check_rollout_columns(feed.F, feed.y_columns, (self.os, self.oe), self._prev_cols, self.k)
         self.reset()
+
+    @staticmethod
+    def _refuse_world(feed):
+        """The resident rollout reads feed.traj in frame layout; a feed built with world_pos= trains on rows that
+        are 3 columns wider (the obstacle displacement), so the model would be fed the wrong columns."""
+        if getattr(feed, "world", False):
+            raise ValueError("the resident rollout does not support a feed built with world_pos= (the Lagrangian "
+                             "rollout is out of scope): it reads the frames in frame layout, without the obstacle "
+                             "displacement columns the model was trained on")
 
     # ------------------------------------------------------------------ trajectory bookkeeping
     def reset(self):
@@ -276,6 +286,7 @@ class Rollout:
         feed = self.feed
         if feed is None:
             raise ValueError("rollout_resident needs Rollout(..., feed=ResidentTrajectories)")
+        self._refuse_world(feed)
         if self.sim.training:
             raise RuntimeError("rollout_resident runs the evaluation forward: call sim.eval() first")
         x, y, d = batch.x, batch.y, self.oe - self.os

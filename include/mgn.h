@@ -579,6 +579,53 @@ int mgn_feed_rotate_rows(const float* src, int64_t rows, int32_t cols, int64_t l
                          const int32_t* row_graph /* device, [rows] */, int32_t B, mgn_feed_ranges triples,
                          const float* R /* device, [B, 9] */, float* dst, int64_t ld_dst, mgn_stream_t stream);
 
+/* World positions inside the feed (Lagrangian data: the reference's world_pos_parameters stages,
+ * dataset/preprocessing.py:49-89 add_obstacles_next_pos and :143-174 add_world_pos_features, in the order of
+ * build_preprocessing :401-442: obstacle displacement, then noise, then the relative world positions of the edges).
+ * With a = traj[t, r, :F] (t = frame[g]) and n = traj[t + 1, r, :F], world position in columns [0, 3), the node
+ * type in frame column type_index:
+ *   mgn_feed_batch_world   writes batch rows of width F + 3:
+ *       y[r, j]      = n[y_start + j]                          always clean (y_start must be 0, y_end >= 3)
+ *       disp[r, j]   = n[j] - a[j], j < 3                      from clean values, one rounded fp32 difference
+ *       mean[g][j]   = (sum of disp[r, j] over the rows of g with a[type_index] == 1, OBSTACLE) / (float) M_g
+ *                      an fp32 sum in a fixed order (per thread over rows 1024 apart, a shuffle tree over the
+ *                      wave, the waves in order), then a true, correctly rounded division by the count M_g, as
+ *                      torch.mean: not a product with a reciprocal. M_g == 0 writes 0 (the reference: NaN).
+ *       x[r, 0:3]    = a[0:3]
+ *       x[r, 3:6]    = disp[r] for an OBSTACLE row, mean[g] for any other
+ *       x[r, 6 + c]  = a[3 + c]                                the node type lands in batch column type_index + 3
+ *     then mgn_feed_batch's noise rule on top of that value, with `ranges` in BATCH-layout columns (the
+ *     reference's noise_index_start / _end of such a config), NORMAL rows only, the type read from the clean row,
+ *     the rounded product then the rounded add, never an FMA. obstacle_mean [B, 3] is caller-owned and written.
+ *     Columns of x at or beyond F + 3 are left alone; traj is never written. Two launches: one workgroup per
+ *     graph for the mean, then the fill. No float atomics, no workspace: the same bits on every replay.
+ *   mgn_feed_world_edge_features   for edge e, from the (noisy) x just written, senders = edge_index[0]:
+ *       v = x[senders[e], 0:3] - x[receivers[e], 0:3]
+ *       edge_attr[e, start : start + 3] = v
+ *       edge_attr[e, start + 3]         = sqrt((v0*v0 + v1*v1) + v2*v2)   every product and sum rounded on its
+ *                                         own, the square root correctly rounded
+ *     Other columns of edge_attr are not touched. senders / receivers must lie in [0, rows of x): a precondition
+ *     (the caller validates them once), not checked on the device. One launch, one thread per edge; the four
+ *     values are one 16-byte store when start, ld_ea and the address of edge_attr are multiples of 4 floats.
+ * frame, scales and z are read on the device at run time. No allocation, no synchronisation: capturable.
+ * N == 0, B == 0 and E == 0 return 0 without a launch. Before any launch, a nonzero status for everything
+ * mgn_feed_batch refuses (ranges and ldx checked against F + 3), F < 4, type_index < 3 or >= F, y_start != 0,
+ * y_end < 3, a noisy range containing batch column type_index + 3, obstacle_mean == NULL; for the edge features
+ * ld_ea < start + 4, start < 0, ldx < 3, null pointers with E > 0. Not covered: world edges that change from
+ * frame to frame (the edge list is static), the Lagrangian rollout, previous_data, rotation together with world
+ * positions. The added symbols do not change MGN_ABI_VERSION; MGN_HAS_FEED_WORLD marks headers that declare them. */
+#define MGN_HAS_FEED_WORLD 1
+int mgn_feed_batch_world(const float* traj, int64_t T, int64_t N, int32_t F, const int32_t* graph_ptr, int32_t B,
+                         const int32_t* frame, int32_t y_start, int32_t y_end,
+                         int32_t type_index,                   /* node-type column of a FRAME row, in [3, F) */
+                         mgn_feed_ranges ranges,               /* noisy columns of a BATCH row, inside [0, F + 3] */
+                         const float* scales, const float* z, int64_t ldz,
+                         float* x, int64_t ldx /* >= F + 3 */, float* y, int64_t ldy,
+                         float* obstacle_mean /* device, [B, 3], written */, mgn_stream_t stream);
+int mgn_feed_world_edge_features(const int32_t* senders /* device, [E] */, const int32_t* receivers /* device, [E] */,
+                                 int64_t E, const float* x, int64_t ldx, float* edge_attr, int64_t ld_ea,
+                                 int32_t start, mgn_stream_t stream);
+
 /* Resident rollout: the data work of one autoregressive validation step (reference lightning_module.py:17-25,
  * 168-249) around the Simulator's evaluation forward, driven by a step counter on the device (*cursor, int32),
  * so a trajectory is S replays of one captured begin -> forward -> end. traj, graph_ptr and frame as in
