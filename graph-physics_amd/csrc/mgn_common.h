@@ -175,6 +175,67 @@ __device__ __forceinline__ int graph_of_row(const int32_t* __restrict__ graph_pt
     return lo;
 }
 
+// The mean obstacle displacement of one graph, by one workgroup of WORLD_MEAN_THREADS threads (every thread of it
+// calls this; it holds a barrier): rows [r0, r1) of the frame at cur and of the next frame at nxt, both [N, F]
+// with the world position in columns [0, 3). A thread walks the rows WORLD_MEAN_THREADS apart and adds the
+// displacement n[j] - a[j] of its OBSTACLE rows; the 64 lanes of a wave are summed by a shuffle tree, the wave
+// sums by thread 0 in wave order: a fixed order, so the same bits on every replay, and the same bits from
+// mgn_feed_batch_world and mgn_rollout_begin_world, which both reduce here. Thread 0 writes mean[0..3).
+constexpr int WORLD_MEAN_THREADS = 1024;
+
+__device__ __forceinline__ void world_obstacle_mean_of_graph(const float* __restrict__ cur,
+                                                             const float* __restrict__ nxt, int F, int64_t r0,
+                                                             int64_t r1, int type_index, float* __restrict__ mean) {
+#pragma clang fp contract(off)
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    int m = 0;
+    for (int64_t r = r0 + threadIdx.x; r < r1; r += WORLD_MEAN_THREADS) {
+        const float* a = cur + r * F;
+        const float* n = nxt + r * F;
+        if (a[type_index] == 1.f) {  // NodeType.OBSTACLE
+            const float d0 = n[0] - a[0], d1 = n[1] - a[1], d2 = n[2] - a[2];
+            s0 = s0 + d0;
+            s1 = s1 + d1;
+            s2 = s2 + d2;
+            ++m;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {  // lane 0 ends with the wave's sum
+        s0 = s0 + __shfl_down(s0, off, 64);
+        s1 = s1 + __shfl_down(s1, off, 64);
+        s2 = s2 + __shfl_down(s2, off, 64);
+        m += __shfl_down(m, off, 64);
+    }
+    constexpr int WAVES = WORLD_MEAN_THREADS / 64;
+    __shared__ float ws[WAVES][3];
+    __shared__ int wm[WAVES];
+    if ((threadIdx.x & 63) == 0) {
+        const int w = threadIdx.x >> 6;
+        ws[w][0] = s0;
+        ws[w][1] = s1;
+        ws[w][2] = s2;
+        wm[w] = m;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t0 = ws[0][0], t1 = ws[0][1], t2 = ws[0][2];
+        int M = wm[0];
+        for (int w = 1; w < WAVES; ++w) {
+            t0 = t0 + ws[w][0];
+            t1 = t1 + ws[w][1];
+            t2 = t2 + ws[w][2];
+            M += wm[w];
+        }
+        // torch.mean's division by the count (correctly rounded: hipcc's default for fp32 division); a graph
+        // without an OBSTACLE row writes 0 where the reference's mean of nothing is NaN
+        const float cnt = (float)M;
+        mean[0] = M > 0 ? t0 / cnt : 0.f;
+        mean[1] = M > 0 ? t1 / cnt : 0.f;
+        mean[2] = M > 0 ? t2 / cnt : 0.f;
+    }
+}
+
 // --------------------------------------------------------------------------- packed weights
 // Forward fragments of W[n][k] (nn.Linear weight [out, in]):
 //   pack[((nt*KS + ks)*64 + lane)*VEC + v] = W[nt*16 + (lane&15)][ks*KSTEP + VEC*(lane>>4) + v]

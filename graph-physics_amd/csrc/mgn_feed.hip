@@ -185,68 +185,17 @@ __global__ __launch_bounds__(256) void rotate_rows(const float* __restrict__ src
 // ---- world positions (mgn.h, "World positions inside the feed"; reference add_obstacles_next_pos and
 // add_world_pos_features, dataset/preprocessing.py:49-89, 143-174) ----
 //
-// obstacle_mean: one workgroup per graph, so the sum needs no second pass, no workspace and no atomics. A
-// thread walks the graph's rows WORLD_MEAN_THREADS apart and adds the displacement n[j] - a[j] of its OBSTACLE
-// rows; the 64 lanes of a wave are summed by a shuffle tree, the wave sums by thread 0 in wave order: a fixed
-// order, so the same bits on every replay. A row costs two partly used cache lines here (a thread per row); the
-// kernel reads 2·rows·F floats in all, once per fill, and a DeformingPlate graph is about 1.4 k rows.
-constexpr int WORLD_MEAN_THREADS = 1024;
-
+// obstacle_mean: one workgroup per graph, so the sum needs no second pass, no workspace and no atomics: the
+// per-graph reduction of mgn_common.h (world_obstacle_mean_of_graph, shared with the rollout's begin stage), a
+// fixed order, so the same bits on every replay. A row costs two partly used cache lines here (a thread per row);
+// the kernel reads 2·rows·F floats in all, once per fill, and a DeformingPlate graph is about 1.4 k rows.
 __global__ __launch_bounds__(WORLD_MEAN_THREADS) void world_obstacle_mean(
     const float* __restrict__ traj, int64_t N, int F, const int32_t* __restrict__ graph_ptr,
     const int32_t* __restrict__ frame, int type_index, float* __restrict__ mean) {
-#pragma clang fp contract(off)
     const int g = blockIdx.x;
-    const int64_t r0 = graph_ptr[g], r1 = graph_ptr[g + 1];
     const float* cur = traj + (int64_t)frame[g] * N * F;
-    const float* nxt = cur + N * F;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    int m = 0;
-    for (int64_t r = r0 + threadIdx.x; r < r1; r += WORLD_MEAN_THREADS) {
-        const float* a = cur + r * F;
-        const float* n = nxt + r * F;
-        if (a[type_index] == 1.f) {  // NodeType.OBSTACLE
-            const float d0 = n[0] - a[0], d1 = n[1] - a[1], d2 = n[2] - a[2];
-            s0 = s0 + d0;
-            s1 = s1 + d1;
-            s2 = s2 + d2;
-            ++m;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {  // lane 0 ends with the wave's sum
-        s0 = s0 + __shfl_down(s0, off, 64);
-        s1 = s1 + __shfl_down(s1, off, 64);
-        s2 = s2 + __shfl_down(s2, off, 64);
-        m += __shfl_down(m, off, 64);
-    }
-    constexpr int WAVES = WORLD_MEAN_THREADS / 64;
-    __shared__ float ws[WAVES][3];
-    __shared__ int wm[WAVES];
-    if ((threadIdx.x & 63) == 0) {
-        const int w = threadIdx.x >> 6;
-        ws[w][0] = s0;
-        ws[w][1] = s1;
-        ws[w][2] = s2;
-        wm[w] = m;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t0 = ws[0][0], t1 = ws[0][1], t2 = ws[0][2];
-        int M = wm[0];
-        for (int w = 1; w < WAVES; ++w) {
-            t0 = t0 + ws[w][0];
-            t1 = t1 + ws[w][1];
-            t2 = t2 + ws[w][2];
-            M += wm[w];
-        }
-        // torch.mean's division by the count (correctly rounded: hipcc's default for fp32 division); a graph
-        // without an OBSTACLE row writes 0 where the reference's mean of nothing is NaN
-        const float cnt = (float)M;
-        mean[3 * (int64_t)g + 0] = M > 0 ? t0 / cnt : 0.f;
-        mean[3 * (int64_t)g + 1] = M > 0 ? t1 / cnt : 0.f;
-        mean[3 * (int64_t)g + 2] = M > 0 ? t2 / cnt : 0.f;
-    }
+    world_obstacle_mean_of_graph(cur, cur + N * F, F, graph_ptr[g], graph_ptr[g + 1], type_index,
+                                 mean + 3 * (int64_t)g);
 }
 
 // feed_batch on the batch layout [world(3), displacement(3), the other F - 3 frame columns]: one thread per

@@ -14,6 +14,9 @@
 // velocity and position targets): the row's node type, its d targets, outputs and current values are read once
 // and every result of the row is written from registers. Only the final kernel writes the step counter, so by
 // stream order every earlier kernel of the step has read the old value. No atomics.
+//
+// rollout_begin_world is the begin stage for Lagrangian data: the batch row [world(3), obstacle displacement(3),
+// the other frame columns] of mgn_feed_batch_world, noise-free, at frame + step, then the same feedback.
 #include "mgn_common.h"
 
 namespace {
@@ -49,6 +52,70 @@ __global__ __launch_bounds__(256) void rollout_begin(const float* __restrict__ t
     }
     x[r * ldx + c] = v;
     if (c >= y_start && c < y_end) y[r * ldy + (c - y_start)] = src[(int64_t)N * F + c];
+}
+
+// ---- the begin stage on Lagrangian data (mgn.h, "Resident rollout with world positions") ----
+//
+// rollout_world_mean is mgn_feed_batch_world's reduction (world_obstacle_mean_of_graph, mgn_common.h) at frame
+// frame[g] + *cursor: one workgroup per graph, the same order, so the same bits as the feed's at that frame. The
+// step counter and the graph's frame are the same for the whole workgroup, so a step outside the trajectory
+// leaves it as one, ahead of the reduction's barrier.
+__global__ __launch_bounds__(WORLD_MEAN_THREADS) void rollout_world_mean(
+    const float* __restrict__ traj, int64_t T, int64_t N, int F, const int32_t* __restrict__ graph_ptr,
+    const int32_t* __restrict__ frame, const int32_t* __restrict__ cursor, int type_index,
+    float* __restrict__ mean) {
+    const int g = blockIdx.x;
+    const int64_t t = (int64_t)frame[g] + *cursor;
+    if (t < 0 || t > T - 2) return;  // uniform: nothing of this graph is read or written
+    const float* cur = traj + t * N * F;
+    world_obstacle_mean_of_graph(cur, cur + N * F, F, graph_ptr[g], graph_ptr[g + 1], type_index,
+                                 mean + 3 * (int64_t)g);
+}
+
+// feed_batch_world's fill (mgn_feed.hip) without the noise, at frame frame[g] + *cursor, then rollout_begin's
+// feedback in batch-layout columns: one thread per element (r, c) of [N, F + 3], consecutive lanes on
+// consecutive floats of x. The displacement and the mean always come from the clean frames; the thread of a
+// world column c < 3 also stores the clean position into world_clean [N, 3] (12 bytes per row, contiguous over
+// the rows), what the "frame" edge mode gathers from.
+__global__ __launch_bounds__(256) void rollout_begin_world(
+    const float* __restrict__ traj, int64_t T, int64_t N, int F, const int32_t* __restrict__ graph_ptr, int B,
+    const int32_t* __restrict__ frame, const int32_t* __restrict__ cursor, int y_end, int type_index, int o_start,
+    int o_end, int p_start, int p_end, const float* __restrict__ last, int64_t ld_last,
+    const float* __restrict__ last_prev, int64_t ld_prev, float* __restrict__ x, int64_t ldx,
+    float* __restrict__ y, int64_t ldy, const float* __restrict__ mean, float* __restrict__ world_clean) {
+#pragma clang fp contract(off)
+    const int Fx = F + 3;
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t total = N * Fx;
+    if (e >= total) return;
+    int64_t r;
+    if (total <= (int64_t)UINT32_MAX)  // uniform: the 32-bit division where it suffices
+        r = (uint32_t)e / (uint32_t)Fx;
+    else
+        r = e / Fx;
+    const int c = (int)(e - r * Fx);
+    const int g = graph_of_row(graph_ptr, B, r);
+    const int s = *cursor;
+    const int64_t t = (int64_t)frame[g] + s;
+    if (t < 0 || t > T - 2) return;  // as rollout_begin: never read past the trajectory
+    const float* a = traj + (t * N + r) * F;
+    const float* n = a + (int64_t)N * F;
+    float v;
+    if (c < 3)
+        v = a[c];
+    else if (c < 6)
+        v = a[type_index] == 1.f ? n[c - 3] - a[c - 3] : mean[3 * (int64_t)g + (c - 3)];
+    else
+        v = a[c - 3];
+    if (c < 3 && world_clean != nullptr) world_clean[r * 3 + c] = v;
+    if (s > 0) {  // feed the previous prediction back, after the fill (reference _make_prediction)
+        if (c >= o_start && c < o_end)
+            v = last[r * ld_last + (c - o_start)];
+        else if (c >= p_start && c < p_end)
+            v = last_prev[r * ld_prev + (c - p_start)];
+    }
+    x[r * ldx + c] = v;
+    if (c < y_end) y[r * ldy + c] = n[c];  // y_start == 0 (checked on the host)
 }
 
 // part[3 * block] = {Σ m·err, Σ m, Σ err} of the block's rows
@@ -153,6 +220,57 @@ int mgn_rollout_begin(const float* traj, int64_t T, int64_t N, int32_t F, const 
     hipLaunchKernelGGL(rollout_begin, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, traj, T, N, (int)F,
                        graph_ptr, (int)B, frame, cursor, (int)y_start, (int)y_end, (int)out_start, (int)out_end,
                        (int)prev_start, (int)prev_end, last, ld_last, last_prev, ld_prev, x, ldx, y, ldy);
+    MGN_LAUNCH_CHECK();
+    return 0;
+}
+
+int mgn_rollout_begin_world(const float* traj, int64_t T, int64_t N, int32_t F, const int32_t* graph_ptr, int32_t B,
+                            const int32_t* frame, const int32_t* cursor, int32_t y_start, int32_t y_end,
+                            int32_t type_index, int32_t out_start, int32_t out_end, int32_t prev_start,
+                            int32_t prev_end, const float* last, int64_t ld_last, const float* last_prev,
+                            int64_t ld_prev, float* x, int64_t ldx, float* y, int64_t ldy, float* obstacle_mean,
+                            float* world_clean, mgn_stream_t stream) {
+    const std::string who = "rollout_begin_world";
+    MGN_REQUIRE(T >= 2, who + ": a trajectory needs at least 2 frames (x from frame t, y from t + 1)");
+    MGN_REQUIRE(F >= 4 && F <= INT32_MAX - 3, who + ": F must be >= 4 (world position and a node type)");
+    MGN_REQUIRE(N >= 0 && B >= 0, who + ": N and B must be >= 0");
+    MGN_REQUIRE(N <= INT32_MAX, who + ": graph_ptr is int32, N must fit it");
+    const int32_t Fx = F + 3;  // the width of a batch row
+    MGN_REQUIRE(y_start >= 0 && y_start <= y_end && y_end <= F, who + ": the y column range is outside [0, F]");
+    MGN_REQUIRE(y_start == 0 && y_end >= 3, who + ": the y columns must begin with the world position "
+                                                  "(y_start == 0, y_end >= 3)");
+    MGN_REQUIRE(type_index >= 3 && type_index < F,
+                who + ": type_index must be a frame column outside the world position, in [3, F)");
+    MGN_REQUIRE(out_start >= 0 && out_start < out_end && out_end <= Fx,
+                who + ": the output column range must be a non-empty range inside [0, F + 3]");
+    MGN_REQUIRE(prev_start >= 0 && prev_start <= prev_end && prev_end <= Fx,
+                who + ": the previous-data column range is outside [0, F + 3]");
+    MGN_REQUIRE(prev_start == prev_end || prev_start >= out_end || out_start >= prev_end,
+                who + ": the output and previous-data column ranges overlap");
+    MGN_REQUIRE(type_index + 3 < out_start || type_index + 3 >= out_end,
+                who + ": the output column range contains the node type (batch column type_index + 3)");
+    MGN_REQUIRE(prev_start == prev_end || type_index + 3 < prev_start || type_index + 3 >= prev_end,
+                who + ": the previous-data column range contains the node type (batch column type_index + 3)");
+    MGN_REQUIRE(ldx >= Fx, who + ": ldx is smaller than F + 3");
+    MGN_REQUIRE(ldy >= y_end - y_start, who + ": ldy is smaller than the y column count");
+    MGN_REQUIRE(ld_last >= out_end - out_start, who + ": ld_last is smaller than the output column count");
+    MGN_REQUIRE(prev_start == prev_end || ld_prev >= prev_end - prev_start,
+                who + ": ld_prev is smaller than the previous-data column count");
+    MGN_REQUIRE(obstacle_mean != nullptr, who + ": obstacle_mean is null");
+    if (N == 0 || B == 0) return 0;
+    MGN_REQUIRE(traj && graph_ptr && frame && cursor && x && y, who + ": a null pointer argument");
+    MGN_REQUIRE(last != nullptr, who + ": an output column range without last");
+    MGN_REQUIRE(prev_start == prev_end || last_prev != nullptr,
+                who + ": a previous-data column range without last_prev");
+    const int64_t blocks = cdiv64(N * Fx, 256);
+    MGN_REQUIRE(blocks <= INT32_MAX, who + ": N * (F + 3) is too large for one launch");
+    hipLaunchKernelGGL(rollout_world_mean, dim3((unsigned)B), dim3(WORLD_MEAN_THREADS), 0, (hipStream_t)stream, traj,
+                       T, N, (int)F, graph_ptr, frame, cursor, (int)type_index, obstacle_mean);
+    MGN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rollout_begin_world, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, traj, T, N,
+                       (int)F, graph_ptr, (int)B, frame, cursor, (int)y_end, (int)type_index, (int)out_start,
+                       (int)out_end, (int)prev_start, (int)prev_end, last, ld_last, last_prev, ld_prev, x, ldx, y, ldy,
+                       (const float*)obstacle_mean, world_clean);
     MGN_LAUNCH_CHECK();
     return 0;
 }

@@ -191,6 +191,8 @@ EXPORTS = {
     "mgn_feed_world_edge_features": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp]),
     "mgn_rollout_begin": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
                                  _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "mgn_rollout_begin_world": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+                                       _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "mgn_rollout_end_workspace_bytes": (_sz, [_i64]),
     "mgn_rollout_end": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _u32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                _vp, _sz, _vp]),
@@ -678,6 +680,50 @@ def rollout_begin(traj, graph_ptr, frame, cursor, y_columns, out_columns, prev_c
                                   os_, oe, ps, pe, ptr(last), last.stride(0), ptr(last_prev if pe > ps else None),
                                   last_prev.stride(0) if pe > ps else 0, ptr(x), x.stride(0), ptr(y), y.stride(0),
                                   stream_ptr(traj.device)))
+
+
+def rollout_begin_world(traj, graph_ptr, frame, cursor, y_columns, type_index, out_columns, prev_columns, last,
+                        last_prev, x, y, obstacle_mean, world_clean=None):
+    """Step s = cursor of a resident rollout on Lagrangian data, before the forward (mgn_rollout_begin_world):
+    x[:, :F + 3] = [world(3), obstacle displacement(3), the other columns] of frame[g] + s of traj [T, N, F],
+    noise-free and bit for bit what feed_batch_world writes at that frame, then `last` in out_columns and
+    `last_prev` in prev_columns (batch-layout columns) when s > 0; y = y_columns of the next frame;
+    obstacle_mean [B, 3] = the per-graph mean displacement of the OBSTACLE rows; world_clean [N, 3] (None: not
+    kept) = the clean world positions of the frame. type_index is the node-type column of a frame row.
+    prev_columns None (or empty): no previous data. Writes in place on the current stream."""
+    import torch
+
+    fn = "rollout_begin_world"
+    require_device(traj)
+    if traj.dtype != torch.float32 or traj.dim() != 3 or not traj.is_contiguous():
+        raise ValueError(f"{fn}: traj must be a contiguous fp32 [T, N, F] tensor")
+    T, N, F = traj.shape
+    (ys, ye), (os_, oe) = (int(v) for v in y_columns), (int(v) for v in out_columns)
+    ps, pe = (int(v) for v in prev_columns) if prev_columns is not None else (0, 0)
+    _rollout_2d(fn, "x", x, N, traj.device)
+    _rollout_2d(fn, "y", y, N, traj.device, ye - ys)
+    _rollout_2d(fn, "last", last, N, traj.device, oe - os_)
+    if pe > ps:
+        if last_prev is None:
+            raise ValueError(f"{fn}: previous-data columns without last_prev")
+        _rollout_2d(fn, "last_prev", last_prev, N, traj.device, pe - ps)
+    B = frame.numel()
+    for name, t, n in (("graph_ptr", graph_ptr, B + 1), ("frame", frame, B), ("cursor", cursor, 1)):
+        if t.dtype != torch.int32 or t.numel() != n or t.device != traj.device or not t.is_contiguous():
+            raise ValueError(f"{fn}: {name} must be a contiguous int32 tensor of {n} elements on {traj.device}")
+    if x.shape[1] < F + 3:
+        raise ValueError(f"{fn}: x needs at least F + 3 columns")
+    for name, t, rows in (("obstacle_mean", obstacle_mean, B), ("world_clean", world_clean, N)):
+        if t is None and name == "world_clean":  # optional
+            continue
+        if t is None or t.dtype != torch.float32 or tuple(t.shape) != (rows, 3) or not t.is_contiguous() or \
+                t.device != traj.device:
+            raise ValueError(f"{fn}: {name} must be a contiguous fp32 [{rows}, 3] tensor on {traj.device}")
+    check(lib().mgn_rollout_begin_world(ptr(traj), T, N, F, ptr(graph_ptr), B, ptr(frame), ptr(cursor), ys, ye,
+                                        int(type_index), os_, oe, ps, pe, ptr(last), last.stride(0),
+                                        ptr(last_prev if pe > ps else None), last_prev.stride(0) if pe > ps else 0,
+                                        ptr(x), x.stride(0), ptr(y), y.stride(0), ptr(obstacle_mean),
+                                        ptr(world_clean), stream_ptr(traj.device)))
 
 
 def rollout_end_workspace(N, device):

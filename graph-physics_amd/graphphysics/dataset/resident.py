@@ -28,15 +28,18 @@ mgn_feed_world_edge_features writes the relative world positions of the noisy x 
 columns of batch.edge_attr. fill_world_torch / world_edge_features_torch state both rules term by term.
 
 Not supported: `previous_data`, world edges that change from frame to frame (the edge_index given with
-world_pos= is static for the life of the feed: the radius search is not part of the fill), the Lagrangian
-rollout (Rollout refuses a feed built with world_pos=), rotate= together with world_pos=, and trajectories of
-unequal length in one batch. batch.edge_index is never touched, batch.edge_attr only by a rotating feed that
+world_pos= is static for the life of the feed: the radius search is not part of the fill), rotate= together with
+world_pos=, and trajectories of unequal length in one batch. batch.edge_index is never touched, batch.edge_attr only by a rotating feed that
 was given a clean edge_attr and by a world_pos= feed that was given an edge_index.
 
 The validation rollout reads the same resident frames (training.rollout.Rollout.rollout_resident):
 rollout_begin_torch / rollout_end_torch state, as torch ops on any device, the two rules libmgn's
 mgn_rollout_begin / mgn_rollout_end run around the Simulator's evaluation forward; there previous data is
-supported, noise is not applied.
+supported, noise is not applied. On a world_pos= feed (Rollout(..., world_edges=...)) the begin stage is
+mgn_rollout_begin_world, stated by rollout_begin_world_torch on fill_world_torch's own expressions: the
+noise-free batch row of frame start + s, then the feedback in batch-layout columns; the four edge_attr columns
+come from world_edge_features_torch / mgn_feed_world_edge_features, on the clean world positions of the frame or
+on the x the model is about to see, as the caller chooses.
 """
 import math
 
@@ -211,7 +214,9 @@ def check_rollout_columns(F, y_columns, out_columns, prev_columns, node_type_ind
     """The host-side preconditions of a resident rollout (ValueError): the model's output columns, the target
     columns and, when used, the previous-data columns have one width d; the output and previous-data ranges
     lie inside [0, F), do not overlap, and do not contain the node-type column (the rollout writes them,
-    and reads the node type of the written row). Returns d."""
+    and reads the node type of the written row). For a world_pos= feed F is the batch width (the frame's + 3)
+    and the output, previous-data and node-type columns are batch-layout columns; y_columns stay frame columns
+    (only their width is compared). Returns d."""
     (ys, ye), (os_, oe) = (int(v) for v in y_columns), (int(v) for v in out_columns)
     d = oe - os_
     if d < 1 or not 0 <= os_ < oe <= F:
@@ -252,6 +257,44 @@ def rollout_begin_torch(traj, graph_ptr, frame, cursor, y_columns, out_columns, 
     y.copy_(traj[t + 1, rows, y_columns[0]:y_columns[1]])
 
 
+def rollout_begin_world_torch(traj, graph_ptr, frame, cursor, y_columns, type_index, out_columns, prev_columns, last,
+                              last_prev, x, y, obstacle_mean, world_clean=None):
+    """mgn_rollout_begin_world's rule as torch ops on any device, in place on x [N, >= F + 3], y [N, d],
+    obstacle_mean [B, 3] and world_clean [N, 3] (None: not kept): with s = cursor (a one-element int tensor or an
+    int) and t = frame[g] + s, fill_world_torch's noise-free batch of frame t — x[:, :F + 3] = [world(3), obstacle
+    displacement(3), the other frame columns], y = y_columns of frame t + 1, obstacle_mean — then, when s > 0,
+    x[:, out_columns] = last and x[:, prev_columns] = last_prev in BATCH-layout columns (prev_columns None: no
+    previous data): the displacement and the mean always come from the clean frames, as in the reference, whose
+    dataset item is built before _make_prediction writes the prediction back. world_clean = the clean world
+    positions of frame t. type_index is the node-type column of a frame row. A graph whose t is outside [0, T - 2]
+    is left alone: its rows of x, y and world_clean and its row of obstacle_mean. traj is only read. The CPU path
+    of Rollout.rollout_resident on a world_pos= feed, and what the kernel is tested and timed against."""
+    T, N, F = traj.shape
+    s = int(cursor)
+    gp = [int(v) for v in (graph_ptr.tolist() if torch.is_tensor(graph_ptr) else graph_ptr)]
+    t = frame.to(traj.device, torch.int64) + s
+    valid = (t >= 0) & (t <= T - 2)
+    fx, fy, mean = fill_world_torch(traj, gp, t.clamp(0, T - 2), y_columns, type_index, [], None, None)
+    if s > 0:
+        fx[:, out_columns[0]:out_columns[1]] = last
+        if prev_columns is not None and prev_columns[1] > prev_columns[0]:
+            fx[:, prev_columns[0]:prev_columns[1]] = last_prev
+    clean = traj[t.clamp(0, T - 2)[_node_graph(gp, N, traj.device)], torch.arange(N, device=traj.device), 0:3]
+    if bool(valid.all()):
+        x[:, :F + 3] = fx
+        y.copy_(fy)
+        obstacle_mean.copy_(mean)
+        if world_clean is not None:
+            world_clean.copy_(clean)
+        return
+    rows = valid[_node_graph(gp, N, traj.device)]
+    x[:, :F + 3] = torch.where(rows[:, None], fx, x[:, :F + 3])
+    y.copy_(torch.where(rows[:, None], fy, y))
+    obstacle_mean.copy_(torch.where(valid[:, None], mean, obstacle_mean))
+    if world_clean is not None:
+        world_clean.copy_(torch.where(rows[:, None], clean, world_clean))
+
+
 def rollout_end_torch(out, y, x, node_type_index, masks, out_start, last, last_prev, preds, cursor, loss, sq):
     """mgn_rollout_end's rule as torch ops on any device, in place on its state: with s = cursor,
     pred = y where the node type x[:, node_type_index] is neither NORMAL nor OUTFLOW (training.rollout.build_mask)
@@ -287,8 +330,8 @@ class ResidentTrajectories:
 
     frame [B] int32, z [N, W] fp32 (None without noise) and scales [n] fp32 (None without noise) are
     allocated once and only rewritten: a captured graph keeps reading the same addresses, tests and users
-    read there what the last fill used. Not supported: previous_data, per-frame world edges, the Lagrangian
-    rollout, trajectories of unequal length (module docstring).
+    read there what the last fill used. Not supported: previous_data, per-frame world edges, trajectories of
+    unequal length (module docstring).
 
     rotate: None, or the rotation augmentation of the reference's Random3DRotate, one rotation per graph and
     fill, as a dict

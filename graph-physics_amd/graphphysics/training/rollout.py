@@ -23,6 +23,16 @@ on the device as one replay per step of a single captured graph: libmgn's mgn_ro
 the previous prediction fed back when s > 0), the same Simulator eval forward, mgn_rollout_end (mask, feedback
 state, the kept prediction, the step's loss and squared error, s += 1). The step counter s lives on the device;
 the host neither builds per-frame batches nor keeps lists of predictions, and never synchronises.
+
+Lagrangian data (a feed built with world_pos=, e.g. DeformingPlate): Rollout(..., world_edges=MODE) runs the same
+three stages with mgn_rollout_begin_world in front — the batch row [world(3), obstacle displacement(3), the other
+columns] of frame start + s built from clean values, then the feedback in batch-layout columns, as the
+reference's validation does (its dataset item is built first, _make_prediction writes the prediction back after
+it: the displacement is never recomputed) — plus one mgn_feed_world_edge_features launch for the four world
+columns of edge_attr. MODE says which positions those follow, and the caller must choose: "frame", the clean
+world positions of frame start + s (the reference's validation: its edge features are part of the dataset item);
+"prediction", the x the model is about to see, so from step 1 on the fed-back positions; "off", x only (models
+without edge_attr, feeds without an edge side). The default None refuses such a feed.
 """
 import math
 import weakref
@@ -55,7 +65,7 @@ class _Resident:
 
 class Rollout:
     def __init__(self, sim, node_type_index, masks=(NodeType.NORMAL, NodeType.OUTFLOW), use_previous_data=False,
-                 previous_data_start=None, previous_data_end=None, graph=True, feed=None):
+                 previous_data_start=None, previous_data_end=None, graph=True, feed=None, world_edges=None):
         self.sim = sim
         self.k = int(node_type_index)
         self.masks = list(masks)
@@ -69,27 +79,49 @@ class Rollout:
         # feed (dataset.resident.ResidentTrajectories): the trajectories rollout_resident reads. A validation
         # feed of its own: set_frames puts it into explicit mode, a TrainStep sharing it would re-record.
         self.feed = feed
+        # world_edges: None, or for a feed built with world_pos= where the world columns of edge_attr come from:
+        # "frame" (the clean frame), "prediction" (the x the model sees) or "off" (module docstring)
+        self.world_edges = world_edges
         self._res = None  # rollout_resident's state (_Resident)
         self.resident_records = 0  # how many times rollout_resident recorded its graph
         self._res_sq, self._res_count = [], 0  # Σ (pred − target)² per resident run (device), and their elements
         if feed is not None:
             from graphphysics.dataset.resident import check_rollout_columns
 
-            self._refuse_world(feed)
+            world = self._check_world(feed)
             if torch.device(sim.device).type != feed.traj.device.type:
                 raise ValueError(f"feed lives on {feed.traj.device}, the simulator on {sim.device}")
             self._prev_cols = (int(self.ps), int(self.pe)) if self.use_prev else None
-            check_rollout_columns(feed.F, feed.y_columns, (self.os, self.oe), self._prev_cols, self.k)
+            # a world feed: the batch row is 3 wider than the frame's, every index here is in batch layout
+            check_rollout_columns(feed.F + 3 if world else feed.F, feed.y_columns, (self.os, self.oe),
+                                  self._prev_cols, self.k)
         self.reset()
 
-    @staticmethod
-    def _refuse_world(feed):
-        """The resident rollout reads feed.traj in frame layout; a feed built with world_pos= trains on rows that
-        are 3 columns wider (the obstacle displacement), so the model would be fed the wrong columns."""
-        if getattr(feed, "world", False):
-            raise ValueError("the resident rollout does not support a feed built with world_pos= (the Lagrangian "
-                             "rollout is out of scope): it reads the frames in frame layout, without the obstacle "
-                             "displacement columns the model was trained on")
+    WORLD_EDGES = ("frame", "prediction", "off")
+
+    def _check_world(self, feed):
+        """ValueError unless world_edges fits the feed; returns whether the feed was built with world_pos=. The
+        resident rollout of a plain feed reads the frames in frame layout; a world_pos= feed trains on rows that
+        are 3 columns wider (the obstacle displacement), and its rollout has to be told where the world columns
+        of edge_attr come from."""
+        world, mode = bool(getattr(feed, "world", False)), self.world_edges
+        if mode is not None and mode not in self.WORLD_EDGES:
+            raise ValueError(f"world_edges must be None or one of {self.WORLD_EDGES}, got {mode!r}")
+        if world and mode is None:
+            raise ValueError("the resident rollout of a feed built with world_pos= needs Rollout(..., world_edges="
+                             '"frame" | "prediction" | "off"): without it the frames would be read in frame layout, '
+                             "without the obstacle displacement columns the model was trained on")
+        if not world:
+            if mode is not None:
+                raise ValueError(f"world_edges={mode!r} needs a feed built with world_pos=")
+            return False
+        if mode != "off" and feed.senders is None:
+            raise ValueError(f"world_edges={mode!r} needs a feed whose world_pos= has an edge_index and an "
+                             'edge_attr_start; use "off" for a model without edge_attr')
+        if self.k != feed.node_type_index + 3:
+            raise ValueError(f"node_type_index {self.k} differs from the feed's node_type_index + 3 = "
+                             f"{feed.node_type_index + 3} (the batch layout of a world_pos= feed)")
+        return True
 
     # ------------------------------------------------------------------ trajectory bookkeeping
     def reset(self):
@@ -201,10 +233,10 @@ class Rollout:
         and buffers of these shapes; keeping the predictions or not is part of what was recorded."""
         if self._res is None:
             return False
-        ref, ver, xs, ys, ea, kept = self._res.key
+        ref, ver, xs, ys, ea, kept, mode = self._res.key
         return (ref() is batch.edge_index and ver == batch.edge_index._version and xs == batch.x.shape
                 and ys == batch.y.shape and ea == (None if batch.edge_attr is None else batch.edge_attr.shape)
-                and kept == keep)
+                and kept == keep and mode == self.world_edges)
 
     def _resident_alloc(self, batch, keep):
         feed, dev = self.feed, batch.x.device
@@ -220,29 +252,50 @@ class Rollout:
         st.loss = torch.zeros(cap, dtype=torch.float32, device=dev)
         st.sq = torch.zeros(cap, dtype=torch.float32, device=dev)
         st.cursor = torch.zeros(1, dtype=torch.int32, device=dev)  # the step counter: only the end stage writes it
+        st.obstacle_mean, st.world_clean = None, None
+        if self.world_edges is not None:  # a world_pos= feed (checked by the caller)
+            st.obstacle_mean = torch.zeros(feed.B, 3, dtype=torch.float32, device=dev)
+            if self.world_edges == "frame":  # the clean world positions of the step's frame: the edges' input
+                st.world_clean = torch.zeros(feed.N, 3, dtype=torch.float32, device=dev)
         st.ws, st.graph, st.topo = None, None, None
         if dev.type == "cuda":
             from graphphysics import _native as nat
 
             st.ws = nat.rollout_end_workspace(feed.N, dev)
         st.key = (weakref.ref(batch.edge_index), batch.edge_index._version, batch.x.shape, batch.y.shape,
-                  None if batch.edge_attr is None else batch.edge_attr.shape, keep)
+                  None if batch.edge_attr is None else batch.edge_attr.shape, keep, self.world_edges)
         return st
 
     def _resident_step(self, st):
         """Step `cursor`: frame and feedback into the static batch, the evaluation forward, mask / state /
         results. Three stages of device work and nothing else, so it records as it runs."""
-        feed = self.feed
+        feed, mode = self.feed, self.world_edges
         if st.x.is_cuda:
             from graphphysics import _native as nat
 
             begin, end, extra = nat.rollout_begin, nat.rollout_end, (st.ws,)
+            begin_world = nat.rollout_begin_world
         else:
             from graphphysics.dataset.resident import rollout_begin_torch as begin, rollout_end_torch as end
+            from graphphysics.dataset.resident import rollout_begin_world_torch as begin_world
 
             extra = ()
-        begin(feed.traj, feed.graph_ptr, feed.frame, st.cursor, feed.y_columns, (self.os, self.oe), self._prev_cols,
-              st.last, st.last_prev, st.x, st.y)
+        if mode is None:
+            begin(feed.traj, feed.graph_ptr, feed.frame, st.cursor, feed.y_columns, (self.os, self.oe),
+                  self._prev_cols, st.last, st.last_prev, st.x, st.y)
+        else:
+            begin_world(feed.traj, feed.graph_ptr, feed.frame, st.cursor, feed.y_columns, feed.node_type_index,
+                        (self.os, self.oe), self._prev_cols, st.last, st.last_prev, st.x, st.y, st.obstacle_mean,
+                        st.world_clean)
+            if mode != "off":  # "frame": the clean positions of the frame; "prediction": what the model sees
+                pos = st.world_clean if mode == "frame" else st.x
+                if st.x.is_cuda:
+                    nat.feed_world_edge_features(feed.senders, feed.receivers, pos, st.edge_attr,
+                                                 feed.edge_attr_start)
+                else:
+                    from graphphysics.dataset.resident import world_edge_features_torch
+
+                    world_edge_features_torch(pos, feed._world_edge_index, st.edge_attr, feed.edge_attr_start)
         with torch.no_grad():
             _, _, out = self.sim(st.frame)
         end(out, st.y, st.x, self.k, self.masks, self.os, st.last, st.last_prev, st.preds, st.cursor, st.loss, st.sq,
@@ -279,23 +332,31 @@ class Rollout:
         forms), the same three stages run eagerly per step.
 
         batch: the static x [N, >= F], y [N, d], edge_index, edge_attr (None for transformer models) and pos;
-        cloned like TrainStep's (x's columns beyond F and edge_attr are re-read on every call). start: an int
+        cloned like TrainStep's (x's columns beyond F and edge_attr are re-read on every call). With a world_pos=
+        feed (world_edges=, module docstring) x is [N, >= F + 3] and, unless the mode is "off", edge_attr is
+        [E, >= edge_attr_start + 4]: the step rewrites those four columns of its own copy, never the caller's. start: an int
         or one int per graph; steps: default T − 1 − max(start). Returns the predictions [steps, N, d] (None
         with keep_predictions=False); extends self.losses by the per-step losses (0-dim device tensors) and
         adds to what all_rollout_rmse() reports. Nothing here synchronises with the host."""
         feed = self.feed
         if feed is None:
             raise ValueError("rollout_resident needs Rollout(..., feed=ResidentTrajectories)")
-        self._refuse_world(feed)
+        world = self._check_world(feed)
         if self.sim.training:
             raise RuntimeError("rollout_resident runs the evaluation forward: call sim.eval() first")
         x, y, d = batch.x, batch.y, self.oe - self.os
         if x.device != feed.traj.device or x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != feed.N or \
-                x.shape[1] < feed.F or self.k >= x.shape[1]:
-            raise ValueError(f"batch.x must be fp32 [{feed.N}, >= {max(feed.F, self.k + 1)}] on {feed.traj.device}, "
+                x.shape[1] < feed.Fx or self.k >= x.shape[1]:
+            raise ValueError(f"batch.x must be fp32 [{feed.N}, >= {max(feed.Fx, self.k + 1)}] on {feed.traj.device}, "
                              f"got {tuple(x.shape)} {x.dtype} on {x.device}")
         if y is None or y.device != x.device or y.dtype != torch.float32 or tuple(y.shape) != (feed.N, d):
             raise ValueError(f"batch.y must be fp32 [{feed.N}, {d}] on {feed.traj.device}")
+        if world and self.world_edges != "off":
+            ea, E, A = getattr(batch, "edge_attr", None), feed.senders.numel(), feed.edge_attr_start + 4
+            if ea is None or ea.device != x.device or ea.dtype != torch.float32 or ea.dim() != 2 or \
+                    ea.shape[0] != E or ea.shape[1] < A or ea.stride(1) != 1:
+                raise ValueError(f"batch.edge_attr must be fp32 [{E}, >= {A}] on {feed.traj.device} with unit column "
+                                 "stride")
         if torch.is_tensor(start):
             start = start.tolist()
         starts = [int(s) for s in start] if isinstance(start, (list, tuple)) else [int(start)] * feed.B

@@ -612,8 +612,8 @@ int mgn_feed_rotate_rows(const float* src, int64_t rows, int32_t cols, int64_t l
  * mgn_feed_batch refuses (ranges and ldx checked against F + 3), F < 4, type_index < 3 or >= F, y_start != 0,
  * y_end < 3, a noisy range containing batch column type_index + 3, obstacle_mean == NULL; for the edge features
  * ld_ea < start + 4, start < 0, ldx < 3, null pointers with E > 0. Not covered: world edges that change from
- * frame to frame (the edge list is static), the Lagrangian rollout, previous_data, rotation together with world
- * positions. The added symbols do not change MGN_ABI_VERSION; MGN_HAS_FEED_WORLD marks headers that declare them. */
+ * frame to frame (the edge list is static), previous_data, rotation together with world positions; the
+ * Lagrangian rollout is mgn_rollout_begin_world below. The added symbols do not change MGN_ABI_VERSION; MGN_HAS_FEED_WORLD marks headers that declare them. */
 #define MGN_HAS_FEED_WORLD 1
 int mgn_feed_batch_world(const float* traj, int64_t T, int64_t N, int32_t F, const int32_t* graph_ptr, int32_t B,
                          const int32_t* frame, int32_t y_start, int32_t y_end,
@@ -667,6 +667,49 @@ int mgn_rollout_end(const float* out, const float* y, const float* x, int64_t N,
                     uint32_t loss_type_mask, int32_t out_start, int32_t d, float* last, float* last_prev,
                     float* preds, int32_t capacity, int32_t* cursor, float* loss, float* sq, void* ws,
                     size_t ws_bytes, mgn_stream_t stream);
+
+/* Resident rollout with world positions (Lagrangian data such as DeformingPlate): the begin stage of a validation
+ * step on the batch layout of mgn_feed_batch_world, following the reference's lightning_module.py:168-232 over a
+ * dataset item built by dataset/preprocessing.py:49-89, 143-174, 401-427. With s = *cursor, t = frame[g] + s,
+ * a = traj[t, r, :F] and n = traj[t + 1, r, :F]:
+ *   mgn_rollout_begin_world
+ *     the noise-free fill: y, disp, mean[g] and x[r, 0 : F + 3] exactly as mgn_feed_batch_world writes them with
+ *       frame[g] = t and z == NULL, bit for bit, obstacle_mean included: both run one per-graph reduction (the
+ *       same order: per thread over rows 1024 apart, a shuffle tree over the wave, the waves in order; a true
+ *       division by the count; 0 for a graph without an OBSTACLE row);
+ *     the feedback, after the fill and only when s > 0, in BATCH-layout columns:
+ *       x[r, out_start + j]  = last[r, j]          x[r, prev_start + j] = last_prev[r, j]
+ *       disp and mean always come from the clean frames: as in the reference, neither is recomputed from the
+ *       fed-back positions;
+ *     world_clean[r, 0:3] = a[0:3] when world_clean is non-null ([N, 3] contiguous): the clean world positions
+ *       of frame t.
+ *   The relative world positions of the edges need no kernel of their own: call mgn_feed_world_edge_features
+ *   after this stage, with x = world_clean, ldx = 3 for edge features that follow the ground-truth frame (the
+ *   reference's validation), or with the batch x for edge features that follow the positions the model sees (from
+ *   step 1 on the fed-back ones). mgn_rollout_end is used as it is, with the batch-layout type_index (the frame's
+ *   + 3), out_start and ldx.
+ * Two launches: one workgroup per graph for the mean, then the fill, one thread per element of [N, F + 3]. No
+ * float atomics, no workspace: the same bits on every replay. *cursor is only read; mgn_rollout_end's final pass
+ * remains its only writer. If t is outside [0, T-2] nothing of that graph is written — its rows of x, y and
+ * world_clean, obstacle_mean[g] — and nothing is read out of bounds. traj is never written; columns of x at or
+ * beyond F + 3 are left alone. N == 0 or B == 0 returns 0 without a launch. No allocation, no synchronisation:
+ * capturable. Before any launch, a nonzero status for everything mgn_rollout_begin refuses (ranges and ldx
+ * checked against F + 3), F < 4, type_index < 3 or >= F, y_start != 0, y_end < 3 or > F, an output or
+ * previous-data range containing batch column type_index + 3, obstacle_mean == NULL (also at N == 0), last == NULL
+ * with a non-empty output range, last_prev == NULL with a non-empty previous-data range. Not covered: world edges
+ * that change from frame to frame, rotation together with world positions. The added symbol does not change
+ * MGN_ABI_VERSION; MGN_HAS_ROLLOUT_WORLD marks headers that declare it. */
+#define MGN_HAS_ROLLOUT_WORLD 1
+int mgn_rollout_begin_world(const float* traj, int64_t T, int64_t N, int32_t F,
+                            const int32_t* graph_ptr, int32_t B, const int32_t* frame, const int32_t* cursor,
+                            int32_t y_start, int32_t y_end,
+                            int32_t type_index,                    /* node-type column of a FRAME row, in [3, F) */
+                            int32_t out_start, int32_t out_end,    /* BATCH-layout columns, inside [0, F + 3] */
+                            int32_t prev_start, int32_t prev_end,  /* BATCH layout; equal: none */
+                            const float* last, int64_t ld_last, const float* last_prev, int64_t ld_prev,
+                            float* x, int64_t ldx /* >= F + 3 */, float* y, int64_t ldy,
+                            float* obstacle_mean /* device, [B, 3], written */,
+                            float* world_clean /* device, [N, 3] contiguous, or NULL */, mgn_stream_t stream);
 
 /* ---------------------------------------------------------------- gated MLP (transformer block, dense half) */
 /* The second line of the reference's Transformer block (layers.py:198-262, 548-627), x + gated_mlp(norm2(x)):
