@@ -327,6 +327,144 @@ int check_feed(const std::string& who, int64_t T, int64_t N, int32_t F, int32_t 
     return 0;
 }
 
+// ---- aneurysm features (mgn.h, "Aneurysm features inside the feed"; reference external/aneurysm.py
+// build_features, then add_noise) ----
+//
+// inflow_stats: one workgroup per (graph, frame) pair, so the value set of a pair lives in one LDS array and needs
+// no workspace and no atomics. The 3·M components of next − current on the graph's inflow rows (and one 0.0 when
+// the graph has a row that is not inflow) are gathered, padded with +inf to a power of two and sorted by a bitonic
+// network: 256 threads walk the P / 2 compare-exchanges of a stage 256 apart, a barrier between stages. Thread 0
+// then walks the sorted values once: a value equal to its predecessor is skipped (the reference's .unique()), the
+// others are added in fp64 in ascending order. The order is a function of the values alone, so the bits depend on
+// neither B, nor the graph's place in the batch, nor the launch geometry. d + 0.0f turns -0.0 into +0.0: the two
+// are one value, and min / max must not depend on which of them the network left in front.
+constexpr int INFLOW_THREADS = 256;
+
+__global__ __launch_bounds__(INFLOW_THREADS) void inflow_stats(const float* __restrict__ traj, int64_t N, int F,
+                                                               const int32_t* __restrict__ graph_ptr, int B,
+                                                               const int32_t* __restrict__ inflow_ptr,
+                                                               const int32_t* __restrict__ inflow_rows,
+                                                               float* __restrict__ stats) {
+#pragma clang fp contract(off)
+    __shared__ float vals[MGN_FEED_INFLOW_CAPACITY];
+    const int g = blockIdx.x;
+    const int64_t t = blockIdx.y;
+    const int i0 = inflow_ptr[g];
+    const int M = inflow_ptr[g + 1] - i0;
+    const int rows = graph_ptr[g + 1] - graph_ptr[g];
+    const int zero = M < rows ? 1 : 0;  // the reference's next_acceleration[~inflow] = 0
+    const int64_t cnt = 3 * (int64_t)M + zero;
+    float* out = stats + (t * B + g) * 3;
+    if (M <= 0 || cnt > MGN_FEED_INFLOW_CAPACITY) {  // uniform; the host refuses cnt > capacity before the launch
+        if (threadIdx.x < 3) out[threadIdx.x] = M <= 0 ? 0.f : __builtin_nanf("");
+        return;
+    }
+    int P = 1;
+    while (P < cnt) P <<= 1;
+    const float* cur = traj + t * N * F;
+    const float* nxt = cur + N * F;
+    for (int i = threadIdx.x; i < P; i += INFLOW_THREADS) {
+        float v = __builtin_inff();
+        if (i < 3 * M) {
+            const int m = i / 3, j = i - 3 * m;
+            const int64_t r = inflow_rows[i0 + m];
+            v = 0.f;
+            if (r >= 0 && r < N) v = (nxt[r * F + j] - cur[r * F + j]) + 0.f;
+        } else if (i < cnt) {
+            v = 0.f;
+        }
+        vals[i] = v;
+    }
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = threadIdx.x; i < P; i += INFLOW_THREADS) {
+                const int o = i ^ j;
+                if (o > i) {
+                    const float a = vals[i], b = vals[o];
+                    if ((i & k) == 0 ? a > b : a < b) {
+                        vals[i] = b;
+                        vals[o] = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    if (threadIdx.x == 0) {
+        double sum = 0.0;
+        int n = 0;
+        float prev = 0.f;
+        for (int i = 0; i < (int)cnt; ++i) {
+            const float v = vals[i];
+            if (i == 0 || v != prev) {
+                sum = sum + (double)v;
+                ++n;
+            }
+            prev = v;
+        }
+        out[0] = (float)(sum / (double)n);
+        out[1] = vals[0];
+        out[2] = vals[cnt - 1];
+    }
+}
+
+// feed_batch on the batch layout [frame row (F) ‖ a − p (3) ‖ pos (3) ‖ mean, min, max ‖ node type]: one thread
+// per element (r, c) of [N, F + 10], so x (when ldx == F + 10) is written as one contiguous span. p is the frame
+// before a (frame[g] >= 1, the host's check). The thread of a y column c < F also copies that column of the next
+// frame. The node type comes from its own array (built once from frame 0), the statistics from row
+// (frame[g], g) of the table inflow_stats wrote.
+__global__ __launch_bounds__(256) void feed_batch_aneurysm(
+    const float* __restrict__ traj, int64_t N, int F, const int32_t* __restrict__ graph_ptr, int B,
+    const int32_t* __restrict__ frame, int y_start, int y_end, const float* __restrict__ pos,
+    const float* __restrict__ node_type, const float* __restrict__ stats, mgn_feed_ranges8 rg,
+    const float* __restrict__ scales, const float* __restrict__ z, int64_t ldz, float* __restrict__ x, int64_t ldx,
+    float* __restrict__ y, int64_t ldy) {
+#pragma clang fp contract(off)  // x + z·s: a rounded product, then a rounded sum (see feed_batch)
+    const int Fx = F + 10;
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t total = N * Fx;
+    if (e >= total) return;
+    int64_t r;
+    if (total <= (int64_t)UINT32_MAX)
+        r = (uint32_t)e / (uint32_t)Fx;
+    else
+        r = e / Fx;
+    const int c = (int)(e - r * Fx);
+    const int g = graph_of_row(graph_ptr, B, r);
+    const int64_t t = frame[g];
+    const float* a = traj + (t * N + r) * F;
+    const float type = node_type[r];
+    float v;
+    if (c < F)
+        v = a[c];
+    else if (c < F + 3)
+        v = a[c - F] - (a - (int64_t)N * F)[c - F];
+    else if (c < F + 6)
+        v = pos[r * 3 + (c - F - 3)];
+    else if (c < F + 9)
+        v = stats[(t * B + g) * 3 + (c - F - 6)];
+    else
+        v = type;
+    if (z != nullptr) {
+        int zc = -1, which = 0, w = 0;
+#pragma unroll
+        for (int i = 0; i < MGN_FEED_ANEURYSM_MAX_RANGES; ++i)
+            if (i < rg.n) {
+                if (c >= rg.start[i] && c < rg.end[i]) {
+                    zc = w + c - rg.start[i];
+                    which = i;
+                }
+                w += rg.end[i] - rg.start[i];
+            }
+        if (zc >= 0 && type == 0.f) {
+            const float noise = z[r * ldz + zc] * scales[which];
+            v = v + noise;
+        }
+    }
+    x[r * ldx + c] = v;
+    if (c >= y_start && c < y_end) y[r * ldy + (c - y_start)] = (a + (int64_t)N * F)[c];
+}
+
 }  // namespace
 
 extern "C" {
@@ -464,6 +602,71 @@ int mgn_feed_world_edge_features(const int32_t* senders, const int32_t* receiver
     else
         hipLaunchKernelGGL(world_edge_features<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                            senders, receivers, E, x, ldx, edge_attr, ld_ea, (int)start);
+    MGN_LAUNCH_CHECK();
+    return 0;
+}
+
+int32_t mgn_feed_inflow_capacity(void) { return MGN_FEED_INFLOW_CAPACITY; }
+
+int mgn_feed_inflow_stats(const float* traj, int64_t T, int64_t N, int32_t F, const int32_t* graph_ptr, int32_t B,
+                          const int32_t* inflow_ptr, const int32_t* inflow_rows, int64_t max_values, float* stats,
+                          mgn_stream_t stream) {
+    const std::string who = "feed_inflow_stats";
+    MGN_REQUIRE(T >= 2, who + ": a trajectory needs at least 2 frames (the statistics of frame t read t + 1)");
+    MGN_REQUIRE(F >= 4, who + ": F must be >= 4 (velocity and the wall flag)");
+    MGN_REQUIRE(N >= 0 && B >= 0, who + ": N and B must be >= 0");
+    MGN_REQUIRE(N <= INT32_MAX, who + ": graph_ptr is int32, N must fit it");
+    MGN_REQUIRE(max_values >= 0, who + ": max_values must be >= 0");
+    MGN_REQUIRE(max_values <= MGN_FEED_INFLOW_CAPACITY,
+                who + ": a graph's value set exceeds the capacity of " + std::to_string(MGN_FEED_INFLOW_CAPACITY) +
+                    " values");
+    MGN_REQUIRE(T - 1 <= 65535, who + ": more than 65535 frames with a successor in one launch");
+    if (N == 0 || B == 0) return 0;
+    MGN_REQUIRE(traj && graph_ptr && inflow_ptr && stats && (inflow_rows || max_values <= 1),
+                who + ": a null pointer argument");
+    hipLaunchKernelGGL(inflow_stats, dim3((unsigned)B, (unsigned)(T - 1)), dim3(INFLOW_THREADS), 0,
+                       (hipStream_t)stream, traj, N, (int)F, graph_ptr, (int)B, inflow_ptr, inflow_rows, stats);
+    MGN_LAUNCH_CHECK();
+    return 0;
+}
+
+int mgn_feed_batch_aneurysm(const float* traj, int64_t T, int64_t N, int32_t F, const int32_t* graph_ptr, int32_t B,
+                            const int32_t* frame, int32_t y_start, int32_t y_end, const float* pos,
+                            const float* node_type, const float* stats, mgn_feed_ranges8 ranges, const float* scales,
+                            const float* z, int64_t ldz, float* x, int64_t ldx, float* y, int64_t ldy,
+                            mgn_stream_t stream) {
+    const std::string who = "feed_batch_aneurysm";
+    MGN_REQUIRE(T >= 3, who + ": a trajectory needs at least 3 frames (x from frames t - 1 and t, y from t + 1)");
+    MGN_REQUIRE(F >= 4 && F <= INT32_MAX - 10, who + ": F must be >= 4 (velocity and the wall flag)");
+    MGN_REQUIRE(N >= 0 && B >= 0, who + ": N and B must be >= 0");
+    MGN_REQUIRE(N <= INT32_MAX, who + ": graph_ptr is int32, N must fit it");
+    const int32_t Fx = F + 10;
+    MGN_REQUIRE(ranges.n >= 0 && ranges.n <= MGN_FEED_ANEURYSM_MAX_RANGES, who + ": at most 8 noisy column ranges");
+    int64_t W = 0;
+    for (int i = 0; i < ranges.n; ++i) {
+        MGN_REQUIRE(ranges.start[i] >= 0 && ranges.start[i] <= ranges.end[i] && ranges.end[i] <= Fx,
+                    who + ": a noisy column range is outside [0, F + 10]");
+        for (int j = 0; j < i; ++j)
+            MGN_REQUIRE(ranges.start[i] >= ranges.end[j] || ranges.start[j] >= ranges.end[i] ||
+                            ranges.start[i] == ranges.end[i] || ranges.start[j] == ranges.end[j],
+                        who + ": noisy column ranges overlap");
+        MGN_REQUIRE(ranges.start[i] == ranges.end[i] || ranges.end[i] <= Fx - 1,
+                    who + ": a noisy column range contains the node type (batch column F + 9)");
+        W += ranges.end[i] - ranges.start[i];
+    }
+    MGN_REQUIRE(y_start >= 0 && y_start <= y_end && y_end <= F, who + ": the y column range is outside [0, F]");
+    MGN_REQUIRE(ldx >= Fx, who + ": ldx is smaller than F + 10");
+    MGN_REQUIRE(ldy >= y_end - y_start, who + ": ldy is smaller than the y column count");
+    MGN_REQUIRE(z == nullptr || ldz >= W, who + ": ldz is smaller than the noisy column count");
+    if (N == 0 || B == 0) return 0;
+    MGN_REQUIRE(traj && graph_ptr && frame && pos && node_type && stats && x && (y || y_start == y_end),
+                who + ": a null pointer argument");
+    MGN_REQUIRE(z == nullptr || W == 0 || scales != nullptr, who + ": noise (z) without scales");
+    const int64_t blocks = cdiv64(N * Fx, 256);
+    MGN_REQUIRE(blocks <= INT32_MAX, who + ": N * (F + 10) is too large for one launch");
+    hipLaunchKernelGGL(feed_batch_aneurysm, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, traj, N, (int)F,
+                       graph_ptr, (int)B, frame, (int)y_start, (int)y_end, pos, node_type, stats, ranges, scales,
+                       W > 0 ? z : nullptr, ldz, x, ldx, y, ldy);
     MGN_LAUNCH_CHECK();
     return 0;
 }

@@ -79,6 +79,16 @@ class FeedRanges(ctypes.Structure):
     _fields_ = [("n", _i32), ("start", _i32 * MGN_FEED_MAX_RANGES), ("end", _i32 * MGN_FEED_MAX_RANGES)]
 
 
+MGN_FEED_ANEURYSM_MAX_RANGES = 8
+MGN_FEED_INFLOW_CAPACITY = 4096  # mgn.h: values per (frame, graph) set of mgn_feed_inflow_stats; checked by load()
+
+
+class FeedRanges8(ctypes.Structure):
+    """mgn_feed_ranges8: the noisy column ranges of mgn_feed_batch_aneurysm, passed by value (mgn.h)."""
+    _fields_ = [("n", _i32), ("start", _i32 * MGN_FEED_ANEURYSM_MAX_RANGES),
+                ("end", _i32 * MGN_FEED_ANEURYSM_MAX_RANGES)]
+
+
 class GatedMlp(ctypes.Structure):
     """mgn_gated_mlp: the fp32 master parameters of a Transformer block's norm2 + gated_mlp (mgn.h)."""
     _fields_ = [("hidden", _i32), ("expand", _i32), ("dtype", _i32), ("norm_dim", _i32), ("max_blocks", _i32),
@@ -189,6 +199,10 @@ EXPORTS = {
     "mgn_feed_batch_world": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _i32, FeedRanges, _vp, _vp,
                                     _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "mgn_feed_world_edge_features": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp]),
+    "mgn_feed_inflow_capacity": (_i32, []),
+    "mgn_feed_inflow_stats": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "mgn_feed_batch_aneurysm": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, FeedRanges8,
+                                       _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "mgn_rollout_begin": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
                                  _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "mgn_rollout_begin_world": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
@@ -255,6 +269,9 @@ def load(path=LIB_PATH):
     if lib.mgn_abi_version() != ABI_VERSION:  # a stale build would mis-read changed signatures
         raise RuntimeError(f"libmgn ABI {lib.mgn_abi_version()} at {path}, these bindings need {ABI_VERSION}: "
                            "rebuild (python __graft_entry__.py)")
+    if lib.mgn_feed_inflow_capacity() != MGN_FEED_INFLOW_CAPACITY:
+        raise RuntimeError(f"libmgn at {path} was built with MGN_FEED_INFLOW_CAPACITY = "
+                           f"{lib.mgn_feed_inflow_capacity()}, these bindings say {MGN_FEED_INFLOW_CAPACITY}")
     _lib = lib
     return lib
 
@@ -639,6 +656,79 @@ def feed_world_edge_features(senders, receivers, x, edge_attr, start):
                              "device with unit column stride")
     check(lib().mgn_feed_world_edge_features(ptr(senders), ptr(receivers), E, ptr(x), x.stride(0), ptr(edge_attr),
                                              edge_attr.stride(0), int(start), stream_ptr(x.device)))
+
+
+def feed_ranges8(ranges):
+    """mgn_feed_ranges8 of [(start, end), ...] (at most MGN_FEED_ANEURYSM_MAX_RANGES; the library checks the values)."""
+    ranges = list(ranges)
+    if len(ranges) > MGN_FEED_ANEURYSM_MAX_RANGES:
+        raise ValueError(f"at most {MGN_FEED_ANEURYSM_MAX_RANGES} noisy column ranges, got {len(ranges)}")
+    r = FeedRanges8()
+    r.n = len(ranges)
+    for i, (s, e) in enumerate(ranges):
+        r.start[i], r.end[i] = int(s), int(e)
+    return r
+
+
+def feed_inflow_stats(traj, graph_ptr, inflow_ptr, inflow_rows, max_values, stats):
+    """stats[t, g] = (mean, min, max) of the distinct next-frame accelerations on the inflow rows of graph g, for
+    every frame t with a successor (mgn_feed_inflow_stats; the rule: dataset.resident.inflow_stats_torch).
+    graph_ptr / inflow_ptr: int32 [B + 1] device tensors, inflow_rows: int32 rows of the batch grouped by graph,
+    max_values: the largest value-set size over the graphs (host int), stats: contiguous fp32 [T - 1, B, 3], written
+    in place on the current stream."""
+    import torch
+
+    require_device(traj)
+    if traj.dtype != torch.float32 or traj.dim() != 3 or not traj.is_contiguous():
+        raise ValueError("feed_inflow_stats: traj must be a contiguous fp32 [T, N, F] tensor")
+    T, N, F = traj.shape
+    B = graph_ptr.numel() - 1
+    for name, t, n in (("graph_ptr", graph_ptr, B + 1), ("inflow_ptr", inflow_ptr, B + 1),
+                       ("inflow_rows", inflow_rows, None)):
+        if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.device != traj.device or \
+                (n is not None and t.numel() != n):
+            raise ValueError(f"feed_inflow_stats: {name} must be a contiguous int32 tensor on traj's device"
+                             + (f" of {n} elements" if n is not None else ""))
+    if stats.dtype != torch.float32 or tuple(stats.shape) != (T - 1, B, 3) or not stats.is_contiguous() or \
+            stats.device != traj.device:
+        raise ValueError(f"feed_inflow_stats: stats must be a contiguous fp32 [{T - 1}, {B}, 3] tensor on traj's "
+                         "device")
+    check(lib().mgn_feed_inflow_stats(ptr(traj), T, N, F, ptr(graph_ptr), B, ptr(inflow_ptr), ptr(inflow_rows),
+                                      int(max_values), ptr(stats), stream_ptr(traj.device)))
+
+
+def feed_batch_aneurysm(traj, graph_ptr, frame, y_columns, pos, node_type, stats, ranges, scales, z, x, y):
+    """One aneurysm training batch from resident trajectories (mgn_feed_batch_aneurysm): x[:, :F + 10] = [frame row ‖
+    a − p ‖ pos ‖ mean, min, max ‖ node type] of frame[g] of traj [T, N, F], plus z * scales on the noisy ranges
+    (batch-layout columns) of the rows with node_type == 0; y = y_columns of the next clean frame. pos fp32 [N, 3],
+    node_type fp32 [N], stats fp32 [T - 1, B, 3] (feed_inflow_stats), all contiguous. Writes x and y in place on the
+    current stream."""
+    import torch
+
+    require_device(traj)
+    if traj.dtype != torch.float32 or traj.dim() != 3 or not traj.is_contiguous():
+        raise ValueError("feed_batch_aneurysm: traj must be a contiguous fp32 [T, N, F] tensor")
+    T, N, F = traj.shape
+    B = frame.numel()
+    for name, t, rows in (("x", x, N), ("y", y, N), ("z", z, N)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != rows or
+                              (t.shape[1] > 1 and t.stride(1) != 1) or t.device != traj.device):
+            raise ValueError(f"feed_batch_aneurysm: {name} must be an fp32 [{rows}, cols] tensor on traj's device "
+                             "with unit column stride")
+    if graph_ptr.dtype != torch.int32 or frame.dtype != torch.int32 or graph_ptr.numel() != B + 1:
+        raise ValueError("feed_batch_aneurysm: graph_ptr [B+1] and frame [B] must be int32 tensors")
+    if x.shape[1] < F + 10 or y.shape[1] != y_columns[1] - y_columns[0]:
+        raise ValueError("feed_batch_aneurysm: x needs at least F + 10 columns and y exactly y_columns[1] - "
+                         "y_columns[0]")
+    for name, t, shape in (("pos", pos, (N, 3)), ("node_type", node_type, (N,)), ("stats", stats, (T - 1, B, 3))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != traj.device:
+            raise ValueError(f"feed_batch_aneurysm: {name} must be a contiguous fp32 {list(shape)} tensor on traj's "
+                             "device")
+    rg = ranges if isinstance(ranges, FeedRanges8) else feed_ranges8(ranges)
+    check(lib().mgn_feed_batch_aneurysm(ptr(traj), T, N, F, ptr(graph_ptr), B, ptr(frame), int(y_columns[0]),
+                                        int(y_columns[1]), ptr(pos), ptr(node_type), ptr(stats), rg, ptr(scales),
+                                        ptr(z), z.stride(0) if z is not None else 0, ptr(x), x.stride(0), ptr(y),
+                                        y.stride(0), stream_ptr(traj.device)))
 
 
 def _rollout_2d(fn, name, t, rows, dev, cols=None):

@@ -27,10 +27,21 @@ fill) with the noise on top, in batch-layout columns; then, when the feed was gi
 mgn_feed_world_edge_features writes the relative world positions of the noisy x and their norm into four
 columns of batch.edge_attr. fill_world_torch / world_edge_features_torch state both rules term by term.
 
-Not supported: `previous_data`, world edges that change from frame to frame (the edge_index given with
-world_pos= is static for the life of the feed: the radius search is not part of the fill), rotate= together with
-world_pos=, and trajectories of unequal length in one batch. batch.edge_index is never touched, batch.edge_attr only by a rotating feed that
-was given a clean edge_attr and by a world_pos= feed that was given an edge_index.
+Aneurysm features (aneurysm=; the reference's external/aneurysm.py build_features, which its train.py hard-wires
+as extra_node_features and coarse-aneurysm.json / c-a-gmm.json are written for): the batch row is [frame row (F) ‖
+a − p (3) ‖ pos (3) ‖ mean, min, max ‖ node type], a the drawn frame and p the one before it, so this mode does
+read the previous frame; the three statistics, over the distinct next-frame accelerations of the graph's inflow
+nodes, are computed once for every (frame, graph) by mgn_feed_inflow_stats (a sort in LDS per pair, an fp64 sum in
+ascending order) and picked by the fill, mgn_feed_batch_aneurysm, one launch with the noise on top in batch-layout
+columns (up to 8 ranges here: the configs have six). inflow_stats_torch / fill_aneurysm_torch state both rules;
+graphphysics.external.aneurysm.build_features is the per-item transform on the same rules.
+
+Not supported: `previous_data` outside aneurysm= (there it is the frame before the drawn one), world edges that
+change from frame to frame (the edge_index given with world_pos= is static for the life of the feed: the radius
+search is not part of the fill), rotate= together with world_pos=, aneurysm= together with either, the resident
+rollout of an aneurysm= feed, and trajectories of unequal length in one batch. batch.edge_index is never touched,
+batch.edge_attr only by a rotating feed that was given a clean edge_attr and by a world_pos= feed that was given an
+edge_index.
 
 The validation rollout reads the same resident frames (training.rollout.Rollout.rollout_resident):
 rollout_begin_torch / rollout_end_torch state, as torch ops on any device, the two rules libmgn's
@@ -65,9 +76,9 @@ def _noise_lists(noise):
     return [int(s) for s in start], [int(e) for e in end], [float(s) for s in scale]
 
 
-def _check_ranges(ranges, F):
-    if len(ranges) > nat.MGN_FEED_MAX_RANGES:
-        raise ValueError(f"at most {nat.MGN_FEED_MAX_RANGES} noisy column ranges are supported, got {len(ranges)}")
+def _check_ranges(ranges, F, limit=nat.MGN_FEED_MAX_RANGES):
+    if len(ranges) > limit:
+        raise ValueError(f"at most {limit} noisy column ranges are supported, got {len(ranges)}")
     for i, (s, e) in enumerate(ranges):
         if not 0 <= s <= e <= F:
             raise ValueError(f"noisy column range ({s}, {e}) is outside [0, {F}]")
@@ -193,6 +204,63 @@ def fill_world_torch(traj, graph_ptr, frame, y_columns, node_type_index, ranges,
             x[:, s:e] = torch.where(normal, feature + noise, feature)
             zc += e - s
     return x, y, mean
+
+
+def inflow_stats_torch(cur, nxt, inflow_mask):
+    """mgn_feed_inflow_stats' rule for one (frame, graph) pair, on any device: fp32 [3] = (mean, min, max) of the
+    value set S of the reference's build_features (external/aneurysm.py: next_acceleration[~inflow] = 0; .unique()).
+    d = nxt[:, 0:3] − cur[:, 0:3], one rounded fp32 subtraction; S = the 3·M components of d on the M inflow rows,
+    plus 0.0 when at least one row is not inflow; equal values (==, so -0.0 and 0.0 are one value, kept as +0.0)
+    count once. min and max are exact. mean = the fp64 sum of the distinct values in ascending order, one addition
+    after the other, divided in fp64 by their count and rounded once to fp32: the kernel's bits. The reference
+    takes torch.mean of the fp32 set, in fp32 and with whatever order its reduction has, so this mean may differ
+    from the reference's by the error of that fp32 sum, |mean − m_ref| <= 2^-24·|m_ref| + 2^-24·Σ|v| over the
+    distinct values v, and is the more accurate of the two. S is never empty for N >= 1 (no rows: zeros). With
+    non-finite values the result is unspecified. The sum runs on the host (a sequential fp64 sum is what the
+    kernel's one thread does; a device reduction orders it otherwise)."""
+    dev = cur.device
+    if cur.shape[0] == 0:
+        return torch.zeros(3, dtype=torch.float32, device=dev)
+    mask = inflow_mask.to(dev, torch.bool)
+    d = nxt[:, 0:3] - cur[:, 0:3]
+    vals = d[mask].reshape(-1)
+    if not bool(mask.all()):
+        vals = torch.cat([vals, torch.zeros(1, dtype=torch.float32, device=dev)])
+    distinct = torch.unique(vals + 0.0).tolist()  # ascending; -0.0 + 0.0 = +0.0
+    total = 0.0
+    for v in distinct:  # Python floats are fp64: the kernel's sum, term by term
+        total += v
+    return torch.tensor([total / len(distinct), distinct[0], distinct[-1]], dtype=torch.float32, device=dev)
+
+
+def fill_aneurysm_torch(traj, graph_ptr, frame, pos, node_type, stats, y_columns, ranges, scales, z):
+    """mgn_feed_batch_aneurysm's rule as torch ops on any device: returns (x [N, F + 10], y [N, y_end - y_start]) as
+    new tensors. With t = frame[g], a = traj[t], p = traj[t − 1] and n = traj[t + 1]: x = [a (F) ‖ a[:, 0:3] −
+    p[:, 0:3] ‖ pos (3) ‖ stats[t, g] = mean, min, max ‖ node_type], the row of the reference's build_features
+    (graphphysics.external.aneurysm); then fill_torch's noise — a rounded product, then a rounded sum, on the rows
+    whose node_type is NORMAL — with `ranges` in the columns of this batch layout; every column draws its own
+    normal, so the noise on the velocity and on the acceleration is independent, as in the reference, whose
+    add_noise runs after build_features. y = the y_columns of n. stats: fp32 [T − 1, B, 3], inflow_stats_torch of
+    every (frame, graph). z None: no noise. What ResidentTrajectories(aneurysm=...).fill runs on CPU tensors, and
+    what the kernel is tested against."""
+    T, N, F = traj.shape
+    dev = traj.device
+    rows = torch.arange(N, device=dev)
+    node_graph = _node_graph(graph_ptr, N, dev)
+    t = frame.to(dev, torch.int64)[node_graph]
+    a, p, n = traj[t, rows], traj[t - 1, rows], traj[t + 1, rows]
+    y = n[:, y_columns[0]:y_columns[1]].contiguous()
+    x = torch.cat([a, a[:, 0:3] - p[:, 0:3], pos.to(dev), stats.to(dev)[t, node_graph], node_type.to(dev)[:, None]],
+                  dim=1)
+    if z is not None:
+        normal = (node_type.to(dev) == NodeType.NORMAL)[:, None]
+        zc = 0
+        for i, (s, e) in enumerate(ranges):
+            feature = x[:, s:e]
+            noise = z[:, zc:zc + e - s] * scales[i]
+            x[:, s:e] = torch.where(normal, feature + noise, feature)
+            zc += e - s
+    return x, y
 
 
 def world_edge_features_torch(x, edge_index, edge_attr, start):
@@ -330,8 +398,8 @@ class ResidentTrajectories:
 
     frame [B] int32, z [N, W] fp32 (None without noise) and scales [n] fp32 (None without noise) are
     allocated once and only rewritten: a captured graph keeps reading the same addresses, tests and users
-    read there what the last fill used. Not supported: previous_data, per-frame world edges, trajectories of
-    unequal length (module docstring).
+    read there what the last fill used. Not supported: previous_data (except with aneurysm=, below), per-frame
+    world edges, trajectories of unequal length (module docstring).
 
     rotate: None, or the rotation augmentation of the reference's Random3DRotate, one rotation per graph and
     fill, as a dict
@@ -357,13 +425,26 @@ class ResidentTrajectories:
     >= 3). Every graph needs an OBSTACLE node: checked on frame 0, node types are assumed constant over the
     frames. obstacle_mean [B, 3] is persistent like frame and z; senders / receivers [E] int32 are built once.
     With an edge side fill writes batch.edge_attr[:, edge_attr_start : edge_attr_start + 4] from the noisy x and
-    touches no other column (the mesh's Cartesian ‖ Distance columns stay). Not together with rotate=."""
+    touches no other column (the mesh's Cartesian ‖ Distance columns stay). Not together with rotate=.
+
+    aneurysm: None, or {"pos": pos} — pos fp32 [N, 3] on the feed's device, static and only read — for the row of
+    the reference's external/aneurysm.py build_features. Frame rows are [velocity (3), wall flag (column 3), ...],
+    F >= 4, T >= 3. The batch row is F + 10 wide, [frame row ‖ a − p ‖ pos ‖ mean, min, max ‖ node type], so
+    node_type_index and the noise's node_type_index are the batch column F + 9, and the noise's indices are in
+    that layout too (up to 8 ranges in this mode). Built once, persistent and only rewritten like frame and z:
+    node_type [N] from frame 0 (the wall flag is assumed constant over the frames, as world_pos= assumes of node
+    types), inflow_ptr [B + 1] / inflow_rows (the inflow nodes of every graph) and inflow_stats [T − 1, B, 3],
+    the statistics of every frame that has a successor; refresh_stats() recomputes that table. Frames are drawn
+    over [1, T − 2] (frame t − 1 is read) and set_frames refuses 0. A graph whose inflow nodes make more than
+    MGN_FEED_INFLOW_CAPACITY values is refused. Not together with rotate= or world_pos=; Rollout refuses such a
+    feed."""
 
     ROTATE_KEYS = ("feature_indices", "edge_attr", "edge_index", "edge_feature_indices")
     WORLD_KEYS = ("world_pos_index_start", "world_pos_index_end", "node_type_index", "edge_index", "edge_attr_start")
+    ANEURYSM_KEYS = ("pos",)
 
     def __init__(self, traj, graph_ptr, y_columns, node_type_index, noise=None, frames="random", rotate=None,
-                 world_pos=None):
+                 world_pos=None, aneurysm=None):
         if not torch.is_tensor(traj) or traj.dtype != torch.float32 or traj.dim() != 3 or not traj.is_contiguous():
             raise ValueError("traj must be a contiguous fp32 [T, N, F] tensor")
         T, N, F = traj.shape
@@ -375,7 +456,16 @@ class ResidentTrajectories:
         ys, ye = int(y_columns[0]), int(y_columns[1])
         if not 0 <= ys < ye <= F:
             raise ValueError(f"y_columns ({ys}, {ye}) must be a non-empty range inside [0, {F}]")
-        if not 0 <= int(node_type_index) < F:
+        # aneurysm=: the batch row is [frame row ‖ a − p ‖ pos ‖ mean, min, max ‖ node type], 10 wider than a frame
+        # row, and the node type is its last column, F + 9: no column of a frame row
+        self.aneurysm = aneurysm is not None
+        if self.aneurysm:
+            if rotate is not None or world_pos is not None:
+                raise ValueError("aneurysm= together with rotate= or world_pos= is not supported")
+            if int(node_type_index) != F + 9:
+                raise ValueError(f"with aneurysm=, node_type_index {node_type_index} must be the batch column F + 9 = "
+                                 f"{F + 9} (the last column of the row build_features makes)")
+        elif not 0 <= int(node_type_index) < F:
             raise ValueError(f"node_type_index {node_type_index} is outside [0, {F})")
         self.traj, self.T, self.N, self.F, self.B = traj, T, N, F, len(gp) - 1
         self.y_columns, self.node_type_index = (ys, ye), int(node_type_index)
@@ -389,7 +479,10 @@ class ResidentTrajectories:
             if rotate is not None:
                 raise ValueError("rotate= together with world_pos= is not supported")
             self._init_world(world_pos, gp)
-        self.Fx = F + 3 if self.world else F  # the width of a batch row
+        self.pos, self.node_type, self.inflow_stats, self.inflow_ptr, self.inflow_rows = None, None, None, None, None
+        if self.aneurysm:
+            self._init_aneurysm(aneurysm, gp)
+        self.Fx = F + 10 if self.aneurysm else F + 3 if self.world else F  # the width of a batch row
         type_column = self.node_type_index + 3 if self.world else self.node_type_index
         if noise is not None:
             if int(noise["node_type_index"]) != type_column:
@@ -398,15 +491,18 @@ class ResidentTrajectories:
                                                      if self.world else ""))
             start, end, self._base_scales = _noise_lists(noise)
             self.ranges = list(zip(start, end))
-            _check_ranges(self.ranges, self.Fx)
-            if self.world and any(s <= type_column < e for s, e in self.ranges):
+            if self.aneurysm:
+                _check_ranges(self.ranges, self.Fx, nat.MGN_FEED_ANEURYSM_MAX_RANGES)
+            else:
+                _check_ranges(self.ranges, self.Fx)
+            if (self.world or self.aneurysm) and any(s <= type_column < e for s, e in self.ranges):
                 raise ValueError(f"a noisy column range contains the node type (batch column {type_column})")
             width = sum(e - s for s, e in self.ranges)
             if width > 0:
                 self.scales = torch.tensor(self._base_scales, dtype=torch.float32, device=dev)
                 self.z = torch.zeros(N, width, dtype=torch.float32, device=dev)
-        self._ranges_c = nat.feed_ranges(self.ranges)
-        self.frame = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self._ranges_c = nat.feed_ranges8(self.ranges) if self.aneurysm else nat.feed_ranges(self.ranges)
+        self.frame = torch.full((self.B,), 1 if self.aneurysm else 0, dtype=torch.int32, device=dev)
         self.random_frames = True
         self.set_frames(frames)
         self.triples, self.angles, self.R = [], None, None
@@ -456,6 +552,61 @@ class ResidentTrajectories:
             self.senders, self.receivers = ei[0].to(torch.int32).contiguous(), ei[1].to(torch.int32).contiguous()
             self.edge_attr_start, self._world_edge_index = int(start), ei
         self.obstacle_mean = torch.zeros(self.B, 3, dtype=torch.float32, device=dev)
+
+    def _init_aneurysm(self, an, gp):
+        if not isinstance(an, dict) or any(k not in self.ANEURYSM_KEYS for k in an) or "pos" not in an:
+            raise ValueError(f"aneurysm must be a dict with keys among {self.ANEURYSM_KEYS} ('pos' is required), "
+                             f"got {an!r}")
+        dev, F, N, T = self.traj.device, self.F, self.N, self.T
+        if F < 4:
+            raise ValueError(f"aneurysm needs frame rows [velocity (3), wall flag, ...]: F = {F} >= 4")
+        if T < 3:
+            raise ValueError(f"aneurysm needs at least 3 frames (x reads frames t - 1 and t, y frame t + 1), got T = {T}")
+        pos = an["pos"]
+        if not torch.is_tensor(pos) or pos.dtype != torch.float32 or tuple(pos.shape) != (N, 3) or \
+                pos.device != dev or not pos.is_contiguous():
+            raise ValueError(f"aneurysm pos must be a contiguous fp32 [{N}, 3] tensor on {dev}")
+        from graphphysics.external.aneurysm import node_type_of
+
+        self.pos = pos
+        self.node_type = node_type_of(self.traj[0], pos).contiguous()  # the wall flag of frame 0: assumed constant
+        inflow = self.node_type == NodeType.INFLOW
+        self._inflow_mask = inflow
+        counts = torch.stack([inflow[gp[g]:gp[g + 1]].sum() for g in range(self.B)]).tolist()
+        # the size of a graph's value set: three components per inflow node, and the zero of the other nodes
+        sizes = [3 * m + (1 if m < gp[g + 1] - gp[g] else 0) for g, m in enumerate(counts)]
+        cap = nat.MGN_FEED_INFLOW_CAPACITY
+        for g, values in enumerate(sizes):
+            if values > cap:
+                raise ValueError(f"graph {g} has {counts[g]} inflow nodes: its value set of {values} accelerations "
+                                 f"exceeds the capacity of {cap} values of mgn_feed_inflow_stats")
+        self._max_values = max(sizes)
+        ptr = [0]
+        for m in counts:
+            ptr.append(ptr[-1] + m)
+        self.inflow_ptr = torch.tensor(ptr, dtype=torch.int32, device=dev)
+        self.inflow_rows = torch.nonzero(inflow).reshape(-1).to(torch.int32).contiguous()  # ascending: grouped by graph
+        self.inflow_stats = torch.zeros(T - 1, self.B, 3, dtype=torch.float32, device=dev)
+        self._gp = gp
+        self.refresh_stats()
+
+    def refresh_stats(self):
+        """Recompute inflow_stats [T − 1, B, 3] from traj, in place (after the caller rewrote frames of traj; the
+        node types and the inflow node lists stay those of construction). HIP tensors: one mgn_feed_inflow_stats
+        launch; CPU tensors: inflow_stats_torch per (frame, graph)."""
+        if not self.aneurysm:
+            raise ValueError("refresh_stats: this feed was built without aneurysm=")
+        with torch.no_grad():
+            if self.traj.is_cuda:
+                nat.feed_inflow_stats(self.traj, self.graph_ptr, self.inflow_ptr, self.inflow_rows, self._max_values,
+                                      self.inflow_stats)
+                return
+            gp = self._gp
+            for t in range(self.T - 1):
+                for g in range(self.B):
+                    rows = slice(gp[g], gp[g + 1])
+                    self.inflow_stats[t, g] = inflow_stats_torch(self.traj[t, rows], self.traj[t + 1, rows],
+                                                                 self._inflow_mask[rows])
 
     def _init_rotate(self, rotate, gp):
         if not isinstance(rotate, dict) or any(k not in self.ROTATE_KEYS for k in rotate):
@@ -518,7 +669,7 @@ class ResidentTrajectories:
 
     def set_frames(self, frames):
         """"random": every fill draws its frames. A host list / CPU tensor of B frames, each in [0, T-2]
-        (ValueError otherwise): the fills use these until the next set_frames."""
+        ([1, T-2] with aneurysm=; ValueError otherwise): the fills use these until the next set_frames."""
         if isinstance(frames, str):
             if frames != "random":
                 raise ValueError(f'frames must be "random" or B = {self.B} frame indices, got {frames!r}')
@@ -527,6 +678,9 @@ class ResidentTrajectories:
         fr = [int(f) for f in (frames.tolist() if torch.is_tensor(frames) else frames)]
         if len(fr) != self.B:
             raise ValueError(f"expected one frame per graph ({self.B}), got {len(fr)}")
+        if self.aneurysm and any(f < 1 or f > self.T - 2 for f in fr):
+            raise ValueError(f"with aneurysm=, frames must lie in [1, {self.T - 2}] (frame t needs its predecessor "
+                             f"t - 1 and its successor t + 1), got {fr}")
         if any(f < 0 or f > self.T - 2 for f in fr):
             raise ValueError(f"frames must lie in [0, {self.T - 2}] (frame t needs its successor t + 1), got {fr}")
         self.random_frames = False
@@ -548,7 +702,8 @@ class ResidentTrajectories:
         reference's matrix per graph, fill_torch and rotate_rows_torch. With world_pos=: batch.x[:, :F + 3], one
         mgn_feed_batch_world (two launches) in mgn_feed_batch's place and, with an edge side, one
         mgn_feed_world_edge_features into batch.edge_attr[:, start:start + 4]; CPU tensors: fill_world_torch and
-        world_edge_features_torch."""
+        world_edge_features_torch. With aneurysm=: batch.x[:, :F + 10], one mgn_feed_batch_aneurysm in
+        mgn_feed_batch's place (the statistics table was built at construction); CPU tensors: fill_aneurysm_torch."""
         x, y = batch.x, batch.y
         if x.device != self.traj.device or x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != self.N or \
                 x.shape[1] < self.Fx:
@@ -576,9 +731,21 @@ class ResidentTrajectories:
                                  "stride")
         with torch.no_grad():
             if self.random_frames:
-                self.frame.random_(0, self.T - 1)  # torch.randint(0, T-1, (B,)) into the persistent tensor
+                # torch.randint(0, T-1, (B,)) into the persistent tensor; aneurysm=: frame t - 1 is read too
+                self.frame.random_(1 if self.aneurysm else 0, self.T - 1)
             if self.z is not None:
                 self.z.normal_()
+            if self.aneurysm:
+                if self.traj.is_cuda:
+                    nat.feed_batch_aneurysm(self.traj, self.graph_ptr, self.frame, self.y_columns, self.pos,
+                                            self.node_type, self.inflow_stats, self._ranges_c, self.scales, self.z,
+                                            x, y)
+                else:
+                    fx, fy = fill_aneurysm_torch(self.traj, self.graph_ptr, self.frame, self.pos, self.node_type,
+                                                 self.inflow_stats, self.y_columns, self.ranges, self.scales, self.z)
+                    x[:, :self.Fx] = fx
+                    y.copy_(fy)
+                return batch
             if self.world:
                 if self.traj.is_cuda:
                     nat.feed_batch_world(self.traj, self.graph_ptr, self.frame, self.y_columns, self.node_type_index,

@@ -88,6 +88,10 @@ class Rollout:
         if feed is not None:
             from graphphysics.dataset.resident import check_rollout_columns
 
+            if getattr(feed, "aneurysm", False):
+                raise ValueError("the resident rollout of a feed built with aneurysm= is not supported yet: its "
+                                 "features (acceleration, inflow statistics) are not rebuilt from the prediction "
+                                 "inside the loop; that is a later pull request")
             world = self._check_world(feed)
             if torch.device(sim.device).type != feed.traj.device.type:
                 raise ValueError(f"feed lives on {feed.traj.device}, the simulator on {sim.device}")

@@ -626,6 +626,60 @@ int mgn_feed_world_edge_features(const int32_t* senders /* device, [E] */, const
                                  int64_t E, const float* x, int64_t ldx, float* edge_attr, int64_t ld_ea,
                                  int32_t start, mgn_stream_t stream);
 
+/* Aneurysm features inside the feed (the reference's external/aneurysm.py build_features, which train.py hard-wires
+ * as extra_node_features, then add_noise; coarse-aneurysm.json is written for this row). Frame rows are
+ * [velocity (3), wall flag, ...], F >= 4; pos [N, 3] and node_type [N] are static, caller-owned and only read.
+ *   mgn_feed_inflow_stats   for every frame t in [0, T - 2] and every graph g, one launch, a workgroup per pair:
+ *       S = the 3 * M_g components of traj[t + 1, r, 0:3] - traj[t, r, 0:3] (one rounded fp32 difference) over the
+ *           rows r = inflow_rows[inflow_ptr[g] .. inflow_ptr[g + 1]) of the graph, plus 0.0 when the graph has a row
+ *           that is not listed (M_g < graph_ptr[g + 1] - graph_ptr[g]): what the reference's
+ *           next_acceleration[~inflow] = 0; .unique() yields. Equal values (==; -0.0 and 0.0 are one value, kept
+ *           as +0.0) count once.
+ *       stats[t, g] = { mean, min, max } of S: min and max exact; mean = the fp64 sum of the distinct values in
+ *           ascending order, divided in fp64 by their count, rounded once to fp32. M_g == 0 writes (0, 0, 0).
+ *     The values are sorted in LDS (a bitonic network); no float atomics, no workspace, and the bits depend on
+ *     neither B, nor the graph's place in the batch, nor the launch geometry. A graph's set may hold at most
+ *     MGN_FEED_INFLOW_CAPACITY values (3 * M_g, plus the zero); max_values is the largest such count over the
+ *     graphs, computed by the host that built inflow_ptr. inflow_rows must lie in [0, N) (a row outside counts as
+ *     0.0). Non-finite values: unspecified results, no fault.
+ *   mgn_feed_batch_aneurysm   writes batch rows of width F + 10; with t = frame[g], a = traj[t, r], p = traj[t - 1, r]
+ *     and n = traj[t + 1, r]:
+ *       x[r, 0:F]          = a
+ *       x[r, F:F+3]        = a[0:3] - p[0:3]                one rounded fp32 difference
+ *       x[r, F+3:F+6]      = pos[r]
+ *       x[r, F+6:F+9]      = stats[t, g]                    mean, min, max
+ *       x[r, F+9]          = node_type[r]
+ *       y[r, j]            = n[y_start + j]                 always clean
+ *     then mgn_feed_batch's noise rule on top of that value, with `ranges` (up to 8, a struct of its own) in
+ *     BATCH-layout columns, on the rows with node_type[r] == 0, the rounded product then the rounded add, never an
+ *     FMA. Columns of x at or beyond F + 10 are left alone; traj is never written. One launch. frame[g] must lie in
+ *     [1, T - 2]: a precondition (the caller owns frame), not checked on the device.
+ * Both are asynchronous, allocate nothing and are capturable. N == 0 or B == 0 returns 0 without a launch. Before
+ * any launch, a nonzero status for null pointers, F < 4, T < 2 (stats) or T < 3 (fill), max_values outside
+ * [0, MGN_FEED_INFLOW_CAPACITY], more than 8 ranges, a range outside [0, F + 10], overlapping ranges, a range
+ * that contains column F + 9, a y range outside [0, F], an ld too small. Not covered: the resident rollout of these
+ * features, rotation together with them. The added symbols do not change MGN_ABI_VERSION; MGN_HAS_FEED_ANEURYSM
+ * marks headers that declare them. */
+#define MGN_HAS_FEED_ANEURYSM 1
+#define MGN_FEED_ANEURYSM_MAX_RANGES 8
+#define MGN_FEED_INFLOW_CAPACITY 4096      /* values per (frame, graph) set: 16 KiB of LDS */
+typedef struct mgn_feed_ranges8 {          /* passed by value at launch */
+    int32_t n;                             /* 0..MGN_FEED_ANEURYSM_MAX_RANGES noisy column ranges */
+    int32_t start[MGN_FEED_ANEURYSM_MAX_RANGES], end[MGN_FEED_ANEURYSM_MAX_RANGES];   /* columns of a batch row */
+} mgn_feed_ranges8;
+int32_t mgn_feed_inflow_capacity(void);    /* MGN_FEED_INFLOW_CAPACITY of the library that was built */
+int mgn_feed_inflow_stats(const float* traj, int64_t T, int64_t N, int32_t F, const int32_t* graph_ptr, int32_t B,
+                          const int32_t* inflow_ptr /* device, [B + 1] offsets into inflow_rows */,
+                          const int32_t* inflow_rows /* device, rows of the batch, grouped by graph */,
+                          int64_t max_values /* host: the largest value-set size over the graphs */,
+                          float* stats /* device, [T - 1, B, 3], written */, mgn_stream_t stream);
+int mgn_feed_batch_aneurysm(const float* traj, int64_t T, int64_t N, int32_t F, const int32_t* graph_ptr, int32_t B,
+                            const int32_t* frame /* device, [B], 1 <= frame[g] <= T - 2 */,
+                            int32_t y_start, int32_t y_end, const float* pos /* device, [N, 3] */,
+                            const float* node_type /* device, [N] */, const float* stats /* device, [T - 1, B, 3] */,
+                            mgn_feed_ranges8 ranges, const float* scales, const float* z, int64_t ldz,
+                            float* x, int64_t ldx /* >= F + 10 */, float* y, int64_t ldy, mgn_stream_t stream);
+
 /* Resident rollout: the data work of one autoregressive validation step (reference lightning_module.py:17-25,
  * 168-249) around the Simulator's evaluation forward, driven by a step counter on the device (*cursor, int32),
  * so a trajectory is S replays of one captured begin -> forward -> end. traj, graph_ptr and frame as in
