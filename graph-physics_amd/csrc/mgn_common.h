@@ -236,6 +236,22 @@ __device__ __forceinline__ void world_obstacle_mean_of_graph(const float* __rest
     }
 }
 
+// Element c of the clean aneurysm batch row [frame row (F) ‖ a − p (3) ‖ pos (3) ‖ mean, min, max ‖ node type] of
+// one node (mgn.h, "Aneurysm features inside the feed"): a = the node's row of frame t, p = its row of frame t − 1,
+// pos3 = its position, stats3 = row (t, g) of the inflow statistics table, type = its node type. Only the element's
+// own operands are loaded; the acceleration is one rounded fp32 difference. mgn_feed_batch_aneurysm and
+// mgn_rollout_begin_aneurysm both take the row from here, so both write the same bits.
+__device__ __forceinline__ float aneurysm_row_value(const float* __restrict__ a, const float* __restrict__ p, int F,
+                                                    int c, const float* __restrict__ pos3,
+                                                    const float* __restrict__ stats3, float type) {
+#pragma clang fp contract(off)
+    if (c < F) return a[c];
+    if (c < F + 3) return a[c - F] - p[c - F];
+    if (c < F + 6) return pos3[c - F - 3];
+    if (c < F + 9) return stats3[c - F - 6];
+    return type;
+}
+
 // --------------------------------------------------------------------------- packed weights
 // Forward fragments of W[n][k] (nn.Linear weight [out, in]):
 //   pack[((nt*KS + ks)*64 + lane)*VEC + v] = W[nt*16 + (lane&15)][ks*KSTEP + VEC*(lane>>4) + v]

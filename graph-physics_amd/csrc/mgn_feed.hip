@@ -434,17 +434,8 @@ __global__ __launch_bounds__(256) void feed_batch_aneurysm(
     const int64_t t = frame[g];
     const float* a = traj + (t * N + r) * F;
     const float type = node_type[r];
-    float v;
-    if (c < F)
-        v = a[c];
-    else if (c < F + 3)
-        v = a[c - F] - (a - (int64_t)N * F)[c - F];
-    else if (c < F + 6)
-        v = pos[r * 3 + (c - F - 3)];
-    else if (c < F + 9)
-        v = stats[(t * B + g) * 3 + (c - F - 6)];
-    else
-        v = type;
+    // the clean row: mgn_common.h, shared with the rollout's begin stage
+    float v = aneurysm_row_value(a, a - (int64_t)N * F, F, c, pos + r * 3, stats + (t * B + g) * 3, type);
     if (z != nullptr) {
         int zc = -1, which = 0, w = 0;
 #pragma unroll

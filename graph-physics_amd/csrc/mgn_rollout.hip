@@ -17,6 +17,9 @@
 //
 // rollout_begin_world is the begin stage for Lagrangian data: the batch row [world(3), obstacle displacement(3),
 // the other frame columns] of mgn_feed_batch_world, noise-free, at frame + step, then the same feedback.
+//
+// rollout_begin_aneurysm is the begin stage for aneurysm data: the batch row [frame row, acceleration, pos, inflow
+// statistics, node type] of mgn_feed_batch_aneurysm, noise-free, at frame + step, then the same feedback. One launch.
 #include "mgn_common.h"
 
 namespace {
@@ -116,6 +119,48 @@ __global__ __launch_bounds__(256) void rollout_begin_world(
     }
     x[r * ldx + c] = v;
     if (c < y_end) y[r * ldy + c] = n[c];  // y_start == 0 (checked on the host)
+}
+
+// ---- the begin stage on aneurysm data (mgn.h, "Resident rollout with the aneurysm features") ----
+//
+// feed_batch_aneurysm's fill (mgn_feed.hip) without the noise, at frame frame[g] + *cursor, then rollout_begin's
+// feedback in batch-layout columns: one thread per element (r, c) of [N, F + 10], consecutive lanes on
+// consecutive floats of x. The row comes from aneurysm_row_value (mgn_common.h), as the feed's does. Frame t − 1
+// is read too, so a step is inside the trajectory when 1 <= t <= T − 2; outside it the thread returns before it
+// forms an address. The statistics are row (t, g) of the clean-frame table: the inflow rows are masked back to the
+// target on every step, so a recomputation from the prediction would give the same values.
+__global__ __launch_bounds__(256) void rollout_begin_aneurysm(
+    const float* __restrict__ traj, int64_t T, int64_t N, int F, const int32_t* __restrict__ graph_ptr, int B,
+    const int32_t* __restrict__ frame, const int32_t* __restrict__ cursor, int y_start, int y_end,
+    const float* __restrict__ pos, const float* __restrict__ node_type, const float* __restrict__ stats, int o_start,
+    int o_end, int p_start, int p_end, const float* __restrict__ last, int64_t ld_last,
+    const float* __restrict__ last_prev, int64_t ld_prev, float* __restrict__ x, int64_t ldx,
+    float* __restrict__ y, int64_t ldy) {
+#pragma clang fp contract(off)
+    const int Fx = F + 10;
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t total = N * Fx;
+    if (e >= total) return;
+    int64_t r;
+    if (total <= (int64_t)UINT32_MAX)  // uniform: the 32-bit division where it suffices
+        r = (uint32_t)e / (uint32_t)Fx;
+    else
+        r = e / Fx;
+    const int c = (int)(e - r * Fx);
+    const int g = graph_of_row(graph_ptr, B, r);
+    const int s = *cursor;
+    const int64_t t = (int64_t)frame[g] + s;
+    if (t < 1 || t > T - 2) return;  // frames t − 1, t and t + 1 are read: never leave the trajectory
+    const float* a = traj + (t * N + r) * F;
+    float v = aneurysm_row_value(a, a - (int64_t)N * F, F, c, pos + r * 3, stats + (t * B + g) * 3, node_type[r]);
+    if (s > 0) {  // feed the previous prediction back, after the fill (reference _make_prediction)
+        if (c >= o_start && c < o_end)
+            v = last[r * ld_last + (c - o_start)];
+        else if (c >= p_start && c < p_end)
+            v = last_prev[r * ld_prev + (c - p_start)];
+    }
+    x[r * ldx + c] = v;
+    if (c >= y_start && c < y_end) y[r * ldy + (c - y_start)] = (a + (int64_t)N * F)[c];  // y_end <= F
 }
 
 // part[3 * block] = {Σ m·err, Σ m, Σ err} of the block's rows
@@ -271,6 +316,49 @@ int mgn_rollout_begin_world(const float* traj, int64_t T, int64_t N, int32_t F, 
                        (int)F, graph_ptr, (int)B, frame, cursor, (int)y_end, (int)type_index, (int)out_start,
                        (int)out_end, (int)prev_start, (int)prev_end, last, ld_last, last_prev, ld_prev, x, ldx, y, ldy,
                        (const float*)obstacle_mean, world_clean);
+    MGN_LAUNCH_CHECK();
+    return 0;
+}
+
+int mgn_rollout_begin_aneurysm(const float* traj, int64_t T, int64_t N, int32_t F, const int32_t* graph_ptr,
+                               int32_t B, const int32_t* frame, const int32_t* cursor, int32_t y_start,
+                               int32_t y_end, const float* pos, const float* node_type, const float* stats,
+                               int32_t out_start, int32_t out_end, int32_t prev_start, int32_t prev_end,
+                               const float* last, int64_t ld_last, const float* last_prev, int64_t ld_prev, float* x,
+                               int64_t ldx, float* y, int64_t ldy, mgn_stream_t stream) {
+    const std::string who = "rollout_begin_aneurysm";
+    MGN_REQUIRE(T >= 3, who + ": a trajectory needs at least 3 frames (x from frames t - 1 and t, y from t + 1)");
+    MGN_REQUIRE(F >= 4 && F <= INT32_MAX - 10, who + ": F must be >= 4 (velocity and the wall flag)");
+    MGN_REQUIRE(N >= 0 && B >= 0, who + ": N and B must be >= 0");
+    MGN_REQUIRE(N <= INT32_MAX, who + ": graph_ptr is int32, N must fit it");
+    const int32_t Fx = F + 10;  // the width of a batch row; the node type is its last column
+    MGN_REQUIRE(y_start >= 0 && y_start <= y_end && y_end <= F, who + ": the y column range is outside [0, F]");
+    MGN_REQUIRE(out_start >= 0 && out_start < out_end && out_end <= Fx,
+                who + ": the output column range must be a non-empty range inside [0, F + 10]");
+    MGN_REQUIRE(prev_start >= 0 && prev_start <= prev_end && prev_end <= Fx,
+                who + ": the previous-data column range is outside [0, F + 10]");
+    MGN_REQUIRE(prev_start == prev_end || prev_start >= out_end || out_start >= prev_end,
+                who + ": the output and previous-data column ranges overlap");
+    MGN_REQUIRE(out_end <= Fx - 1, who + ": the output column range contains the node type (batch column F + 9)");
+    MGN_REQUIRE(prev_start == prev_end || prev_end <= Fx - 1,
+                who + ": the previous-data column range contains the node type (batch column F + 9)");
+    MGN_REQUIRE(ldx >= Fx, who + ": ldx is smaller than F + 10");
+    MGN_REQUIRE(ldy >= y_end - y_start, who + ": ldy is smaller than the y column count");
+    MGN_REQUIRE(ld_last >= out_end - out_start, who + ": ld_last is smaller than the output column count");
+    MGN_REQUIRE(prev_start == prev_end || ld_prev >= prev_end - prev_start,
+                who + ": ld_prev is smaller than the previous-data column count");
+    if (N == 0 || B == 0) return 0;
+    MGN_REQUIRE(traj && graph_ptr && frame && cursor && pos && node_type && stats && x && (y || y_start == y_end),
+                who + ": a null pointer argument");
+    MGN_REQUIRE(last != nullptr, who + ": an output column range without last");
+    MGN_REQUIRE(prev_start == prev_end || last_prev != nullptr,
+                who + ": a previous-data column range without last_prev");
+    const int64_t blocks = cdiv64(N * Fx, 256);
+    MGN_REQUIRE(blocks <= INT32_MAX, who + ": N * (F + 10) is too large for one launch");
+    hipLaunchKernelGGL(rollout_begin_aneurysm, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, traj, T, N,
+                       (int)F, graph_ptr, (int)B, frame, cursor, (int)y_start, (int)y_end, pos, node_type, stats,
+                       (int)out_start, (int)out_end, (int)prev_start, (int)prev_end, last, ld_last, last_prev, ld_prev,
+                       x, ldx, y, ldy);
     MGN_LAUNCH_CHECK();
     return 0;
 }

@@ -207,6 +207,8 @@ EXPORTS = {
                                  _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "mgn_rollout_begin_world": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
                                        _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "mgn_rollout_begin_aneurysm": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32,
+                                          _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "mgn_rollout_end_workspace_bytes": (_sz, [_i64]),
     "mgn_rollout_end": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _u32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
                                _vp, _sz, _vp]),
@@ -814,6 +816,47 @@ def rollout_begin_world(traj, graph_ptr, frame, cursor, y_columns, type_index, o
                                         ptr(last_prev if pe > ps else None), last_prev.stride(0) if pe > ps else 0,
                                         ptr(x), x.stride(0), ptr(y), y.stride(0), ptr(obstacle_mean),
                                         ptr(world_clean), stream_ptr(traj.device)))
+
+
+def rollout_begin_aneurysm(traj, graph_ptr, frame, cursor, y_columns, pos, node_type, stats, out_columns,
+                           prev_columns, last, last_prev, x, y):
+    """Step s = cursor of a resident rollout on aneurysm data, before the forward (mgn_rollout_begin_aneurysm):
+    x[:, :F + 10] = [frame row ‖ a − p ‖ pos ‖ mean, min, max ‖ node type] of frame[g] + s of traj [T, N, F],
+    noise-free and bit for bit what feed_batch_aneurysm writes at that frame, then `last` in out_columns and
+    `last_prev` in prev_columns (batch-layout columns) when s > 0; y = y_columns of the next frame. pos fp32 [N, 3],
+    node_type fp32 [N], stats fp32 [T - 1, B, 3] (feed_inflow_stats), all contiguous and only read. prev_columns None
+    (or empty): no previous data. Writes x and y in place on the current stream."""
+    import torch
+
+    fn = "rollout_begin_aneurysm"
+    require_device(traj)
+    if traj.dtype != torch.float32 or traj.dim() != 3 or not traj.is_contiguous():
+        raise ValueError(f"{fn}: traj must be a contiguous fp32 [T, N, F] tensor")
+    T, N, F = traj.shape
+    (ys, ye), (os_, oe) = (int(v) for v in y_columns), (int(v) for v in out_columns)
+    ps, pe = (int(v) for v in prev_columns) if prev_columns is not None else (0, 0)
+    _rollout_2d(fn, "x", x, N, traj.device)
+    _rollout_2d(fn, "y", y, N, traj.device, ye - ys)
+    _rollout_2d(fn, "last", last, N, traj.device, oe - os_)
+    if pe > ps:
+        if last_prev is None:
+            raise ValueError(f"{fn}: previous-data columns without last_prev")
+        _rollout_2d(fn, "last_prev", last_prev, N, traj.device, pe - ps)
+    B = frame.numel()
+    for name, t, n in (("graph_ptr", graph_ptr, B + 1), ("frame", frame, B), ("cursor", cursor, 1)):
+        if t.dtype != torch.int32 or t.numel() != n or t.device != traj.device or not t.is_contiguous():
+            raise ValueError(f"{fn}: {name} must be a contiguous int32 tensor of {n} elements on {traj.device}")
+    if x.shape[1] < F + 10:
+        raise ValueError(f"{fn}: x needs at least F + 10 columns")
+    for name, t, shape in (("pos", pos, (N, 3)), ("node_type", node_type, (N,)), ("stats", stats, (T - 1, B, 3))):
+        if t is None or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or \
+                t.device != traj.device:
+            raise ValueError(f"{fn}: {name} must be a contiguous fp32 {list(shape)} tensor on {traj.device}")
+    check(lib().mgn_rollout_begin_aneurysm(ptr(traj), T, N, F, ptr(graph_ptr), B, ptr(frame), ptr(cursor), ys, ye,
+                                           ptr(pos), ptr(node_type), ptr(stats), os_, oe, ps, pe, ptr(last),
+                                           last.stride(0), ptr(last_prev if pe > ps else None),
+                                           last_prev.stride(0) if pe > ps else 0, ptr(x), x.stride(0), ptr(y),
+                                           y.stride(0), stream_ptr(traj.device)))
 
 
 def rollout_end_workspace(N, device):

@@ -38,10 +38,10 @@ graphphysics.external.aneurysm.build_features is the per-item transform on the s
 
 Not supported: `previous_data` outside aneurysm= (there it is the frame before the drawn one), world edges that
 change from frame to frame (the edge_index given with world_pos= is static for the life of the feed: the radius
-search is not part of the fill), rotate= together with world_pos=, aneurysm= together with either, the resident
-rollout of an aneurysm= feed, and trajectories of unequal length in one batch. batch.edge_index is never touched,
-batch.edge_attr only by a rotating feed that was given a clean edge_attr and by a world_pos= feed that was given an
-edge_index.
+search is not part of the fill), rotate= together with world_pos=, aneurysm= together with either, a wall flag
+that changes over time (aneurysm= takes the node types from frame 0), and trajectories of unequal length in one
+batch. batch.edge_index is never touched, batch.edge_attr only by a rotating feed that was given a clean edge_attr
+and by a world_pos= feed that was given an edge_index.
 
 The validation rollout reads the same resident frames (training.rollout.Rollout.rollout_resident):
 rollout_begin_torch / rollout_end_torch state, as torch ops on any device, the two rules libmgn's
@@ -50,7 +50,11 @@ supported, noise is not applied. On a world_pos= feed (Rollout(..., world_edges=
 mgn_rollout_begin_world, stated by rollout_begin_world_torch on fill_world_torch's own expressions: the
 noise-free batch row of frame start + s, then the feedback in batch-layout columns; the four edge_attr columns
 come from world_edge_features_torch / mgn_feed_world_edge_features, on the clean world positions of the frame or
-on the x the model is about to see, as the caller chooses.
+on the x the model is about to see, as the caller chooses. On an aneurysm= feed (Rollout(..., acceleration=...))
+the begin stage is mgn_rollout_begin_aneurysm, stated by rollout_begin_aneurysm_torch on fill_aneurysm_torch's own
+expressions: the noise-free row of frame start + s (frames start + s − 1 and start + s + 1 are read too), then the
+feedback; the acceleration columns either follow the clean frames or are the previous-data columns, as the caller
+chooses, and the inflow statistics are always those of the clean-frame table.
 """
 import math
 
@@ -284,7 +288,7 @@ def check_rollout_columns(F, y_columns, out_columns, prev_columns, node_type_ind
     lie inside [0, F), do not overlap, and do not contain the node-type column (the rollout writes them,
     and reads the node type of the written row). For a world_pos= feed F is the batch width (the frame's + 3)
     and the output, previous-data and node-type columns are batch-layout columns; y_columns stay frame columns
-    (only their width is compared). Returns d."""
+    (only their width is compared); for an aneurysm= feed F is the batch width too (the frame's + 10). Returns d."""
     (ys, ye), (os_, oe) = (int(v) for v in y_columns), (int(v) for v in out_columns)
     d = oe - os_
     if d < 1 or not 0 <= os_ < oe <= F:
@@ -363,6 +367,37 @@ def rollout_begin_world_torch(traj, graph_ptr, frame, cursor, y_columns, type_in
         world_clean.copy_(torch.where(rows[:, None], clean, world_clean))
 
 
+def rollout_begin_aneurysm_torch(traj, graph_ptr, frame, cursor, y_columns, pos, node_type, stats, out_columns,
+                                 prev_columns, last, last_prev, x, y):
+    """mgn_rollout_begin_aneurysm's rule as torch ops on any device, in place on x [N, >= F + 10] and y [N, d]: with
+    s = cursor (a one-element int tensor or an int) and t = frame[g] + s, fill_aneurysm_torch's noise-free batch of
+    frame t — x[:, :F + 10] = [frame row ‖ a − p ‖ pos ‖ stats[t, g] ‖ node_type], y = y_columns of frame t + 1 —
+    then, when s > 0, x[:, out_columns] = last and x[:, prev_columns] = last_prev in BATCH-layout columns
+    (prev_columns None: no previous data). With prev_columns (F, F + 3) the acceleration columns carry the previous
+    step's predicted − current, the reference's use_previous_data; without them they follow the clean frames. The
+    statistics always come from the clean-frame table, as in the reference, whose dataset item is built before
+    _make_prediction writes the prediction back. A graph whose t is outside [1, T − 2] (frame t − 1 is read too) is
+    left alone: none of its rows of x or y is written. traj, pos, node_type and stats are only read. The CPU path
+    of Rollout.rollout_resident on an aneurysm= feed, and what the kernel is tested and timed against."""
+    T, N, F = traj.shape
+    s = int(cursor)
+    gp = [int(v) for v in (graph_ptr.tolist() if torch.is_tensor(graph_ptr) else graph_ptr)]
+    t = frame.to(traj.device, torch.int64) + s
+    valid = (t >= 1) & (t <= T - 2)
+    fx, fy = fill_aneurysm_torch(traj, gp, t.clamp(1, T - 2), pos, node_type, stats, y_columns, [], None, None)
+    if s > 0:
+        fx[:, out_columns[0]:out_columns[1]] = last
+        if prev_columns is not None and prev_columns[1] > prev_columns[0]:
+            fx[:, prev_columns[0]:prev_columns[1]] = last_prev
+    if bool(valid.all()):
+        x[:, :F + 10] = fx
+        y.copy_(fy)
+        return
+    rows = valid[_node_graph(gp, N, traj.device)]
+    x[:, :F + 10] = torch.where(rows[:, None], fx, x[:, :F + 10])
+    y.copy_(torch.where(rows[:, None], fy, y))
+
+
 def rollout_end_torch(out, y, x, node_type_index, masks, out_start, last, last_prev, preds, cursor, loss, sq):
     """mgn_rollout_end's rule as torch ops on any device, in place on its state: with s = cursor,
     pred = y where the node type x[:, node_type_index] is neither NORMAL nor OUTFLOW (training.rollout.build_mask)
@@ -436,8 +471,8 @@ class ResidentTrajectories:
     types), inflow_ptr [B + 1] / inflow_rows (the inflow nodes of every graph) and inflow_stats [T − 1, B, 3],
     the statistics of every frame that has a successor; refresh_stats() recomputes that table. Frames are drawn
     over [1, T − 2] (frame t − 1 is read) and set_frames refuses 0. A graph whose inflow nodes make more than
-    MGN_FEED_INFLOW_CAPACITY values is refused. Not together with rotate= or world_pos=; Rollout refuses such a
-    feed."""
+    MGN_FEED_INFLOW_CAPACITY values is refused. Not together with rotate= or world_pos=. Its validation rollout:
+    Rollout(..., feed=, acceleration="frame" | "prediction")."""
 
     ROTATE_KEYS = ("feature_indices", "edge_attr", "edge_index", "edge_feature_indices")
     WORLD_KEYS = ("world_pos_index_start", "world_pos_index_end", "node_type_index", "edge_index", "edge_attr_start")

@@ -33,6 +33,18 @@ columns of edge_attr. MODE says which positions those follow, and the caller mus
 world positions of frame start + s (the reference's validation: its edge features are part of the dataset item);
 "prediction", the x the model is about to see, so from step 1 on the fed-back positions; "off", x only (models
 without edge_attr, feeds without an edge side). The default None refuses such a feed.
+
+Aneurysm data (a feed built with aneurysm=): Rollout(..., acceleration=MODE) runs the same three stages with
+mgn_rollout_begin_aneurysm in front — the row [frame row (F) ‖ a − p ‖ pos ‖ mean, min, max ‖ node type] of the
+reference's external/aneurysm.py build_features at frame start + s, from clean values, then the feedback, as the
+reference's validation does (the dataset item is built first, _make_prediction writes into it afterwards). MODE says
+what the acceleration columns [F, F + 3) hold from step 1 on, and the caller must choose, because the reference's
+own default (use_previous_data=False) would feed ground-truth accelerations to a model that predicts velocities:
+"frame", the clean a − p of every step (the reference with use_previous_data=False); "prediction", the previous
+step's predicted − current, i.e. the acceleration columns are the previous-data columns (the reference's train.py
+default, use_previous_data=True with columns 4, 7 on F = 4). The inflow statistics are those of the clean frames in
+both modes: INFLOW rows are masked back to the target on every step, so the prediction would give the same values.
+Start frames lie in [1, T − 2] (frame start − 1 is read). The default None refuses such a feed.
 """
 import math
 import weakref
@@ -65,7 +77,8 @@ class _Resident:
 
 class Rollout:
     def __init__(self, sim, node_type_index, masks=(NodeType.NORMAL, NodeType.OUTFLOW), use_previous_data=False,
-                 previous_data_start=None, previous_data_end=None, graph=True, feed=None, world_edges=None):
+                 previous_data_start=None, previous_data_end=None, graph=True, feed=None, world_edges=None,
+                 acceleration=None):
         self.sim = sim
         self.k = int(node_type_index)
         self.masks = list(masks)
@@ -82,24 +95,78 @@ class Rollout:
         # world_edges: None, or for a feed built with world_pos= where the world columns of edge_attr come from:
         # "frame" (the clean frame), "prediction" (the x the model sees) or "off" (module docstring)
         self.world_edges = world_edges
+        # acceleration: None, or for a feed built with aneurysm= what the acceleration columns hold from step 1 on:
+        # "frame" (the clean frames) or "prediction" (the previous-data channel) (module docstring)
+        self.acceleration = acceleration
+        self._given_prev = (use_previous_data, previous_data_start, previous_data_end)  # as the caller wrote them
         self._res = None  # rollout_resident's state (_Resident)
         self.resident_records = 0  # how many times rollout_resident recorded its graph
         self._res_sq, self._res_count = [], 0  # Σ (pred − target)² per resident run (device), and their elements
         if feed is not None:
             from graphphysics.dataset.resident import check_rollout_columns
 
-            if getattr(feed, "aneurysm", False):
-                raise ValueError("the resident rollout of a feed built with aneurysm= is not supported yet: its "
-                                 "features (acceleration, inflow statistics) are not rebuilt from the prediction "
-                                 "inside the loop; that is a later pull request")
+            self._refuse_aneurysm_without_mode(feed)
             world = self._check_world(feed)
             if torch.device(sim.device).type != feed.traj.device.type:
                 raise ValueError(f"feed lives on {feed.traj.device}, the simulator on {sim.device}")
-            self._prev_cols = (int(self.ps), int(self.pe)) if self.use_prev else None
-            # a world feed: the batch row is 3 wider than the frame's, every index here is in batch layout
-            check_rollout_columns(feed.F + 3 if world else feed.F, feed.y_columns, (self.os, self.oe),
-                                  self._prev_cols, self.k)
+            # an aneurysm= feed: _check_acceleration sets use_prev and the columns and checks them against F + 10
+            if not self._check_acceleration(feed):
+                self._prev_cols = (int(self.ps), int(self.pe)) if self.use_prev else None
+                # a world feed: the batch row is 3 wider than the frame's, every index here is in batch layout
+                check_rollout_columns(feed.F + 3 if world else feed.F, feed.y_columns, (self.os, self.oe),
+                                      self._prev_cols, self.k)
+        elif acceleration is not None:
+            raise ValueError(f"acceleration={acceleration!r} needs feed=, a ResidentTrajectories built with aneurysm=")
         self.reset()
+
+    ACCELERATION = ("frame", "prediction")
+
+    def _refuse_aneurysm_without_mode(self, feed):
+        if getattr(feed, "aneurysm", False) and self.acceleration is None:
+            raise ValueError("the resident rollout of a feed built with aneurysm= is not supported yet without "
+                             'Rollout(..., acceleration="frame" | "prediction"), which says whether the acceleration '
+                             "columns follow the clean frames or the previous prediction; a default is left to a "
+                             "later pull request")
+
+    def _check_acceleration(self, feed):
+        """ValueError unless acceleration= fits the feed and the columns; returns whether the feed was built with
+        aneurysm=. For such a feed this (re)derives use_prev, the previous-data columns and _prev_cols from what
+        the caller gave and the mode, so a mode changed after construction is applied by the next run."""
+        aneurysm, mode = bool(getattr(feed, "aneurysm", False)), self.acceleration
+        if mode is not None and mode not in self.ACCELERATION:
+            raise ValueError(f"acceleration must be None or one of {self.ACCELERATION}, got {mode!r}")
+        if mode is not None and self.world_edges is not None:
+            raise ValueError("acceleration= and world_edges= do not go together: a feed is built with aneurysm= or "
+                             "with world_pos=, never both")
+        if not aneurysm:
+            if mode is not None:
+                raise ValueError(f"acceleration={mode!r} needs a feed built with aneurysm=")
+            return False
+        self._refuse_aneurysm_without_mode(feed)
+        from graphphysics.dataset.resident import check_rollout_columns
+
+        F = feed.F
+        if self.k != F + 9:
+            raise ValueError(f"node_type_index {self.k} differs from F + 9 = {F + 9}, the node-type column of the "
+                             "row an aneurysm= feed writes")
+        use, ps, pe = self._given_prev
+        acc = (F, F + 3)
+        if mode == "prediction":
+            if (self.os, self.oe) != (0, 3):
+                raise ValueError(f'acceleration="prediction" needs the output columns (0, 3), the velocity whose '
+                                 f"step-to-step difference the acceleration columns hold; got ({self.os}, {self.oe})")
+            if not use:
+                use, ps, pe = True, acc[0], acc[1]
+            elif (int(ps), int(pe)) != acc:
+                raise ValueError(f'acceleration="prediction" makes the acceleration columns {acc} the previous-data '
+                                 f"columns; got previous-data columns ({ps}, {pe})")
+        elif use and int(ps) < acc[1] and acc[0] < int(pe):
+            raise ValueError(f'acceleration="frame" keeps the acceleration columns {acc} on the clean frames, but the '
+                             f'previous-data columns ({ps}, {pe}) intersect them; use acceleration="prediction"')
+        self.use_prev, self.ps, self.pe = use, ps, pe
+        self._prev_cols = (int(ps), int(pe)) if use else None
+        check_rollout_columns(F + 10, feed.y_columns, (self.os, self.oe), self._prev_cols, self.k)
+        return True
 
     WORLD_EDGES = ("frame", "prediction", "off")
 
@@ -237,10 +304,10 @@ class Rollout:
         and buffers of these shapes; keeping the predictions or not is part of what was recorded."""
         if self._res is None:
             return False
-        ref, ver, xs, ys, ea, kept, mode = self._res.key
+        ref, ver, xs, ys, ea, kept, mode, acc = self._res.key
         return (ref() is batch.edge_index and ver == batch.edge_index._version and xs == batch.x.shape
                 and ys == batch.y.shape and ea == (None if batch.edge_attr is None else batch.edge_attr.shape)
-                and kept == keep and mode == self.world_edges)
+                and kept == keep and mode == self.world_edges and acc == self.acceleration)
 
     def _resident_alloc(self, batch, keep):
         feed, dev = self.feed, batch.x.device
@@ -267,7 +334,8 @@ class Rollout:
 
             st.ws = nat.rollout_end_workspace(feed.N, dev)
         st.key = (weakref.ref(batch.edge_index), batch.edge_index._version, batch.x.shape, batch.y.shape,
-                  None if batch.edge_attr is None else batch.edge_attr.shape, keep, self.world_edges)
+                  None if batch.edge_attr is None else batch.edge_attr.shape, keep, self.world_edges,
+                  self.acceleration)
         return st
 
     def _resident_step(self, st):
@@ -278,13 +346,17 @@ class Rollout:
             from graphphysics import _native as nat
 
             begin, end, extra = nat.rollout_begin, nat.rollout_end, (st.ws,)
-            begin_world = nat.rollout_begin_world
+            begin_world, begin_aneurysm = nat.rollout_begin_world, nat.rollout_begin_aneurysm
         else:
             from graphphysics.dataset.resident import rollout_begin_torch as begin, rollout_end_torch as end
             from graphphysics.dataset.resident import rollout_begin_world_torch as begin_world
+            from graphphysics.dataset.resident import rollout_begin_aneurysm_torch as begin_aneurysm
 
             extra = ()
-        if mode is None:
+        if self.acceleration is not None:  # an aneurysm= feed: both modes differ only in the previous-data columns
+            begin_aneurysm(feed.traj, feed.graph_ptr, feed.frame, st.cursor, feed.y_columns, feed.pos, feed.node_type,
+                           feed.inflow_stats, (self.os, self.oe), self._prev_cols, st.last, st.last_prev, st.x, st.y)
+        elif mode is None:
             begin(feed.traj, feed.graph_ptr, feed.frame, st.cursor, feed.y_columns, (self.os, self.oe),
                   self._prev_cols, st.last, st.last_prev, st.x, st.y)
         else:
@@ -338,14 +410,16 @@ class Rollout:
         batch: the static x [N, >= F], y [N, d], edge_index, edge_attr (None for transformer models) and pos;
         cloned like TrainStep's (x's columns beyond F and edge_attr are re-read on every call). With a world_pos=
         feed (world_edges=, module docstring) x is [N, >= F + 3] and, unless the mode is "off", edge_attr is
-        [E, >= edge_attr_start + 4]: the step rewrites those four columns of its own copy, never the caller's. start: an int
-        or one int per graph; steps: default T − 1 − max(start). Returns the predictions [steps, N, d] (None
+        [E, >= edge_attr_start + 4]: the step rewrites those four columns of its own copy, never the caller's. With an
+        aneurysm= feed (acceleration=, module docstring) x is [N, >= F + 10] and every start lies in [1, T − 2]. start:
+        an int or one int per graph; steps: default T − 1 − max(start). Returns the predictions [steps, N, d] (None
         with keep_predictions=False); extends self.losses by the per-step losses (0-dim device tensors) and
         adds to what all_rollout_rmse() reports. Nothing here synchronises with the host."""
         feed = self.feed
         if feed is None:
             raise ValueError("rollout_resident needs Rollout(..., feed=ResidentTrajectories)")
         world = self._check_world(feed)
+        self._check_acceleration(feed)
         if self.sim.training:
             raise RuntimeError("rollout_resident runs the evaluation forward: call sim.eval() first")
         x, y, d = batch.x, batch.y, self.oe - self.os

@@ -657,9 +657,10 @@ int mgn_feed_world_edge_features(const int32_t* senders /* device, [E] */, const
  * Both are asynchronous, allocate nothing and are capturable. N == 0 or B == 0 returns 0 without a launch. Before
  * any launch, a nonzero status for null pointers, F < 4, T < 2 (stats) or T < 3 (fill), max_values outside
  * [0, MGN_FEED_INFLOW_CAPACITY], more than 8 ranges, a range outside [0, F + 10], overlapping ranges, a range
- * that contains column F + 9, a y range outside [0, F], an ld too small. Not covered: the resident rollout of these
- * features, rotation together with them. The added symbols do not change MGN_ABI_VERSION; MGN_HAS_FEED_ANEURYSM
- * marks headers that declare them. */
+ * that contains column F + 9, a y range outside [0, F], an ld too small. Not covered: rotation together with these
+ * features, a wall flag that changes over time (node_type is built once); their resident rollout is
+ * mgn_rollout_begin_aneurysm below. The added symbols do not change MGN_ABI_VERSION; MGN_HAS_FEED_ANEURYSM marks
+ * headers that declare them. */
 #define MGN_HAS_FEED_ANEURYSM 1
 #define MGN_FEED_ANEURYSM_MAX_RANGES 8
 #define MGN_FEED_INFLOW_CAPACITY 4096      /* values per (frame, graph) set: 16 KiB of LDS */
@@ -764,6 +765,44 @@ int mgn_rollout_begin_world(const float* traj, int64_t T, int64_t N, int32_t F,
                             float* x, int64_t ldx /* >= F + 3 */, float* y, int64_t ldy,
                             float* obstacle_mean /* device, [B, 3], written */,
                             float* world_clean /* device, [N, 3] contiguous, or NULL */, mgn_stream_t stream);
+
+/* Resident rollout with the aneurysm features: the begin stage of a validation step on the batch layout of
+ * mgn_feed_batch_aneurysm, following the reference's lightning_module.py:168-232 over a dataset item built by
+ * external/aneurysm.py:27-64. With s = *cursor, t = frame[g] + s, a = traj[t, r], p = traj[t - 1, r] and
+ * n = traj[t + 1, r]:
+ *   mgn_rollout_begin_aneurysm
+ *     the noise-free fill: x[r, 0 : F + 10] = [a ‖ a[0:3] - p[0:3] ‖ pos[r] ‖ stats[t, g] ‖ node_type[r]] and
+ *       y[r, j] = n[y_start + j], exactly as mgn_feed_batch_aneurysm writes them with frame[g] = t and z == NULL,
+ *       bit for bit: both kernels take the row from one inline function;
+ *     the feedback, after the fill and only when s > 0, in BATCH-layout columns:
+ *       x[r, out_start + j]  = last[r, j]          x[r, prev_start + j] = last_prev[r, j]
+ *       so previous-data columns (F, F + 3) put the previous step's predicted - current into the acceleration
+ *       columns (the reference's train.py default, use_previous_data = True, 4, 7 on F = 4), and without them the
+ *       acceleration follows the clean frames. Nothing else is recomputed from the prediction: the statistics are
+ *       those of the clean frames, which is also what a recomputation would give, because the INFLOW rows are
+ *       masked back to the target on every step.
+ *   mgn_rollout_end is used as it is, with type_index = F + 9, out_start and ldx of the batch row.
+ * One launch, one thread per element of [N, F + 10]; no atomics, no workspace: the same bits on every replay.
+ * *cursor is only read; mgn_rollout_end's final pass remains its only writer. traj, pos, node_type and stats are
+ * only read. If t is outside [1, T-2] (frame t - 1 is read too) none of that graph's rows of x or y is written and
+ * nothing is read out of bounds. Columns of x at or beyond F + 10 are left alone. N == 0 or B == 0 returns 0 without
+ * a launch. No allocation, no synchronisation: capturable. Before any launch, a nonzero status for everything
+ * mgn_rollout_begin refuses (ranges and ldx checked against F + 10), F < 4, T < 3, a y range outside [0, F], an
+ * output or previous-data range containing column F + 9, null pos, node_type or stats, last == NULL with a
+ * non-empty output range, last_prev == NULL with a non-empty previous-data range. Not covered: rotation together
+ * with the aneurysm features, a wall flag that changes over time (node types are those of frame 0). The added
+ * symbol does not change MGN_ABI_VERSION; MGN_HAS_ROLLOUT_ANEURYSM marks headers that declare it. */
+#define MGN_HAS_ROLLOUT_ANEURYSM 1
+int mgn_rollout_begin_aneurysm(const float* traj, int64_t T, int64_t N, int32_t F,
+                               const int32_t* graph_ptr, int32_t B,
+                               const int32_t* frame /* device, [B]: 1 <= frame[g] + *cursor <= T - 2 */,
+                               const int32_t* cursor, int32_t y_start, int32_t y_end,
+                               const float* pos /* device, [N, 3] */, const float* node_type /* device, [N] */,
+                               const float* stats /* device, [T - 1, B, 3]: mgn_feed_inflow_stats */,
+                               int32_t out_start, int32_t out_end,    /* BATCH-layout columns, inside [0, F + 9] */
+                               int32_t prev_start, int32_t prev_end,  /* BATCH layout; equal: none */
+                               const float* last, int64_t ld_last, const float* last_prev, int64_t ld_prev,
+                               float* x, int64_t ldx /* >= F + 10 */, float* y, int64_t ldy, mgn_stream_t stream);
 
 /* ---------------------------------------------------------------- gated MLP (transformer block, dense half) */
 /* The second line of the reference's Transformer block (layers.py:198-262, 548-627), x + gated_mlp(norm2(x)):
