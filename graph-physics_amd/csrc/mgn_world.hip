@@ -1,0 +1,262 @@
+// Per-frame world edges as a topology, built without the host (mgn.h, "World edges inside the step"), gfx950.
+//
+// The reference's add_world_edges (dataset/preprocessing.py:92-140) runs per sample: cKDTree.query_pairs(radius)
+// over the world positions, the pairs filtered to OBSTACLE–NORMAL, appended to the mesh edges, to_undirected. The
+// result is a new edge_index per sample, so a model whose attention is masked by the adjacency (the transformer
+// configs) sees a new mask per sample. mgn_radius_pairs + mgn_coalesce + mgn_topology_build do that with three host
+// read-backs and two radix sorts; nothing of it can sit in a captured step.
+//
+// Here the mesh adjacency is static CSR (sorted, symmetric, unique) and only the world pairs change, so the
+// (row, col) order of the union is a per-node MERGE of two ascending lists, and the target-sorted order of a
+// symmetric adjacency is the same lists again: no sort of the edge list, no data-dependent launch shape.
+//   world_search   one thread per node i, 256 per workgroup. The candidates — the rows of the graphs the workgroup's
+//                  256 nodes belong to — are staged through LDS in tiles of WORLD_TILE (position and type: 16 bytes a
+//                  candidate, every lane reads the same address, a broadcast). A NORMAL node keeps the OBSTACLE
+//                  nodes of its own graph within the radius, an OBSTACLE node the NORMAL ones; a candidate found in
+//                  the node's mesh list (binary search) is dropped. The survivors go, ascending, into wl[i·W ..],
+//                  their count into wc[i]. Both directions evaluate the same fp64 expression on the same two rows
+//                  (the difference only changes sign), so the lists are symmetric.
+//   world_scan     one workgroup: the exclusive scan of mesh_deg + wc, into col_ptr and row_ptr, and num_edges.
+//   world_merge    eight lanes per node i: mesh[i] and wl[i] are merged into its segment of csc_src / csc_dst (the
+//                  lists share no value, so an entry's merged place is its index plus its rank in the other list),
+//                  and for every merged edge (j → i) the rank of i among j's neighbours (two binary searches) is
+//                  the edge's place in (row, col) order, which gives csc_eid, row_perm and both edge_index rows.
+// Brute force per graph is deliberate: contact sets are small, it needs no bounding box, no grid and no sort, and
+// the order of every list is fixed. Every grid is a function of N alone.
+#include "mgn_common.h"
+
+namespace {
+
+constexpr int WORLD_THREADS = 256;
+constexpr int WORLD_TILE = 1024;
+constexpr int WORLD_CHUNK = 8;
+constexpr int WORLD_MERGE_LANES = 8;  // lanes that share one node's edges in world_merge
+constexpr int WORLD_SCAN_THREADS = 1024;
+
+size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// first position in the ascending a[0, n) whose value is >= v
+__device__ __forceinline__ int lower_bound_i32(const int32_t* __restrict__ a, int n, int v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__global__ __launch_bounds__(WORLD_THREADS) void world_search(
+    const float* __restrict__ pos, int64_t ldp, const float* __restrict__ nt, int64_t ldt,
+    const int32_t* __restrict__ graph_ptr, int B, int N, const int32_t* __restrict__ mesh_ptr,
+    const int32_t* __restrict__ mesh_nbr, int E_m, double r2, int W, int32_t* __restrict__ wl,
+    int32_t* __restrict__ wc, uint32_t* __restrict__ err) {
+#pragma clang fp contract(off)  // (v0·v0 + v1·v1) + v2·v2 in fp64, every product and sum rounded on its own
+    __shared__ f4 cand[WORLD_TILE];  // x, y, z, node type
+    const int b0 = blockIdx.x * WORLD_THREADS;
+    const int b1 = min(N, b0 + WORLD_THREADS);  // b0 < N: the grid is cdiv(N, 256)
+    const int i = b0 + threadIdx.x;
+    const bool active = i < N;
+    // the rows of every graph that owns one of this workgroup's nodes: uniform over the workgroup
+    const int c0 = clampi(graph_ptr[graph_of_row(graph_ptr, B, b0)], 0, N);
+    const int c1 = clampi(graph_ptr[graph_of_row(graph_ptr, B, b1 - 1) + 1], 0, N);
+    int r0 = 0, r1 = 0, m0 = 0, md = 0;
+    float want = -1.f;
+    double px = 0.0, py = 0.0, pz = 0.0;
+    if (active) {
+        const int g = graph_of_row(graph_ptr, B, i);
+        r0 = graph_ptr[g];
+        r1 = graph_ptr[g + 1];
+        const float a = nt[(int64_t)i * ldt];
+        if (a == 0.f) want = 1.f;       // NORMAL looks for OBSTACLE
+        else if (a == 1.f) want = 0.f;  // OBSTACLE looks for NORMAL; every other type (and NaN) has no world edges
+        m0 = clampi(mesh_ptr[i], 0, E_m);
+        md = clampi(mesh_ptr[i + 1], m0, E_m) - m0;
+        const float* p = pos + (int64_t)i * ldp;
+        px = (double)p[0];
+        py = (double)p[1];
+        pz = (double)p[2];
+    }
+    const bool searching = want >= 0.f;
+    int cnt = 0;
+    for (int t0 = c0; t0 < c1; t0 += WORLD_TILE) {
+        const int nc = min(WORLD_TILE, c1 - t0);
+        for (int c = threadIdx.x; c < nc; c += WORLD_THREADS) {
+            const float* p = pos + (int64_t)(t0 + c) * ldp;
+            cand[c] = f4{p[0], p[1], p[2], nt[(int64_t)(t0 + c) * ldt]};
+        }
+        __syncthreads();
+        if (searching) {
+            const int lo = max(r0, t0) - t0, hi = min(r1, t0 + nc) - t0;  // the node's own graph within the tile
+            // WORLD_CHUNK candidates at a time: their LDS reads are issued together, ahead of the tests, so the
+            // wave does not wait for every read on its own
+            for (int c = lo; c < hi; c += WORLD_CHUNK) {
+                f4 q[WORLD_CHUNK];
+#pragma unroll
+                for (int u = 0; u < WORLD_CHUNK; ++u) q[u] = cand[min(c + u, hi - 1)];
+#pragma unroll
+                for (int u = 0; u < WORLD_CHUNK; ++u) {
+                    if (c + u >= hi || q[u][3] != want) continue;
+                    const double v0 = px - (double)q[u][0], v1 = py - (double)q[u][1], v2 = pz - (double)q[u][2];
+                    double d2 = v0 * v0;
+                    d2 = d2 + v1 * v1;
+                    d2 = d2 + v2 * v2;
+                    if (!(d2 <= r2)) continue;
+                    const int j = t0 + c + u;
+                    const int at = lower_bound_i32(mesh_nbr + m0, md, j);
+                    if (at < md && mesh_nbr[m0 + at] == j) continue;  // already a mesh edge: to_undirected keeps one
+                    if (cnt < W) wl[(int64_t)i * W + cnt] = j;
+                    ++cnt;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (active) {
+        wc[i] = cnt < W ? cnt : W;
+        if (cnt > W) atomicOr(err, MGN_ERR_WORLD_CAPACITY);
+    }
+}
+
+// ptr[i] = Σ_{r < i} (mesh_deg[r] + wc[r]) for i in [0, N], into col_ptr and row_ptr; *num_edges = ptr[N]. One
+// workgroup: a thread sums a contiguous chunk, the chunk sums are scanned in LDS (Hillis–Steele), the thread
+// walks its chunk again. Integers: any order gives the same result.
+__global__ __launch_bounds__(WORLD_SCAN_THREADS) void world_scan(const int32_t* __restrict__ mesh_ptr, int E_m,
+                                                                 const int32_t* __restrict__ wc, int N, int E_cap,
+                                                                 int32_t* __restrict__ col_ptr,
+                                                                 int32_t* __restrict__ row_ptr,
+                                                                 int32_t* __restrict__ num_edges) {
+    __shared__ int part[WORLD_SCAN_THREADS];
+    const int chunk = (N + WORLD_SCAN_THREADS - 1) / WORLD_SCAN_THREADS;
+    const int a = min(N, (int)threadIdx.x * chunk), b = min(N, a + chunk);
+    int s = 0;
+    for (int r = a; r < b; ++r) {
+        const int m0 = clampi(mesh_ptr[r], 0, E_m);
+        s += clampi(mesh_ptr[r + 1], m0, E_m) - m0 + wc[r];
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = 1; off < WORLD_SCAN_THREADS; off <<= 1) {
+        const int v = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int run = part[threadIdx.x] - s;  // exclusive
+    for (int r = a; r < b; ++r) {
+        const int v = clampi(run, 0, E_cap);  // a valid mesh never exceeds E_cap; a broken one stays in bounds
+        col_ptr[r] = v;
+        row_ptr[r] = v;
+        const int m0 = clampi(mesh_ptr[r], 0, E_m);
+        run += clampi(mesh_ptr[r + 1], m0, E_m) - m0 + wc[r];
+    }
+    if (threadIdx.x == WORLD_SCAN_THREADS - 1) {
+        const int total = clampi(part[threadIdx.x], 0, E_cap);
+        col_ptr[N] = total;
+        row_ptr[N] = total;
+        *num_edges = total;
+    }
+}
+
+__global__ __launch_bounds__(256) void world_merge(const int32_t* __restrict__ mesh_ptr,
+                                                   const int32_t* __restrict__ mesh_nbr, int E_m,
+                                                   const int32_t* __restrict__ wl, const int32_t* __restrict__ wc,
+                                                   int W, int N, int E_cap, const int32_t* __restrict__ col_ptr,
+                                                   int32_t* __restrict__ csc_src, int32_t* __restrict__ csc_dst,
+                                                   int32_t* __restrict__ csc_eid, int32_t* __restrict__ row_perm,
+                                                   int64_t* __restrict__ edge_index, uint32_t* __restrict__ err) {
+    // WORLD_MERGE_LANES lanes per node, lane s taking the node's edges s, s + 8, ...: the two lists share no value, so
+    // an entry's place in the merged list is its own index plus its rank in the OTHER list; no lane waits for another
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = (int)(t / WORLD_MERGE_LANES), sub = (int)(t % WORLD_MERGE_LANES);
+    if (i >= N) return;
+    const int m0 = clampi(mesh_ptr[i], 0, E_m);
+    const int md = clampi(mesh_ptr[i + 1], m0, E_m) - m0;
+    const int32_t* ma = mesh_nbr + m0;
+    const int32_t* wa = wl + (int64_t)i * W;
+    const int wd = wc[i];
+    const int base = col_ptr[i];
+    bool bad = false;
+    for (int p = sub; p < md + wd; p += WORLD_MERGE_LANES) {
+        int j, at;
+        if (p < md) {
+            j = ma[p];
+            at = p + lower_bound_i32(wa, wd, j);
+        } else {
+            j = wa[p - md];
+            at = p - md + lower_bound_i32(ma, md, j);
+        }
+        if (j < 0 || j >= N) {  // a mesh neighbour outside [0, N): flagged, clamped, every access stays in bounds
+            bad = true;
+            j = clampi(j, 0, N - 1);
+        }
+        // the rank of i among j's neighbours: edge (j → i) is the e-th in (row, col) order
+        const int jm0 = clampi(mesh_ptr[j], 0, E_m);
+        const int jmd = clampi(mesh_ptr[j + 1], jm0, E_m) - jm0;
+        int e = col_ptr[j] + lower_bound_i32(mesh_nbr + jm0, jmd, i) + lower_bound_i32(wl + (int64_t)j * W, wc[j], i);
+        e = clampi(e, 0, E_cap - 1);  // equal to its exact value unless a list overflowed (see MGN_ERR_WORLD_CAPACITY)
+        const int k = base + at;  // at <= md + wd - 1 for sorted, disjoint lists; guarded for anything else
+        if (k >= 0 && k < E_cap) {
+            csc_src[k] = j;
+            csc_dst[k] = i;
+            csc_eid[k] = e;
+            row_perm[e] = k;
+            edge_index[e] = j;
+            edge_index[(int64_t)E_cap + e] = i;
+        }
+    }
+    if (bad) atomicOr(err, MGN_ERR_EDGE_INDEX);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mgn_world_topology_workspace_bytes(int64_t num_nodes, int32_t max_neighbors) {
+    const int64_t n = num_nodes < 1 ? 1 : num_nodes, w = max_neighbors < 1 ? 1 : max_neighbors;
+    return al((size_t)n * 4) + al((size_t)n * (size_t)w * 4);
+}
+
+int mgn_world_topology_build(const float* pos, int64_t ld_pos, const float* node_type, int64_t ld_type,
+                             const int32_t* graph_ptr, int32_t B, int64_t N, const int32_t* mesh_ptr,
+                             const int32_t* mesh_nbr, int64_t E_m, double radius, int32_t W, int32_t* csc_src,
+                             int32_t* csc_dst, int32_t* csc_eid, int32_t* col_ptr, int32_t* row_ptr, int32_t* row_perm,
+                             int64_t* edge_index, int32_t* num_edges, uint32_t* err_word, void* ws, size_t ws_bytes,
+                             mgn_stream_t stream) {
+    const std::string who = "world_topology_build";
+    MGN_REQUIRE(N >= 0 && B >= 0 && E_m >= 0, who + ": N, B and E_m must be >= 0");
+    MGN_REQUIRE(W >= 1, who + ": max_neighbors must be >= 1");
+    MGN_REQUIRE(radius > 0.0 && std::isfinite(radius), who + ": radius must be positive and finite");
+    MGN_REQUIRE(ld_pos >= 3, who + ": ld_pos is smaller than 3");
+    MGN_REQUIRE(ld_type >= 1, who + ": ld_type must be >= 1");
+    MGN_REQUIRE(N <= (1ll << 30) && E_m <= INT32_MAX && E_m + N * (int64_t)W <= INT32_MAX,
+                who + ": N must be <= 2^30 and E_m + N * max_neighbors must fit int32");
+    MGN_REQUIRE(err_word != nullptr, who + ": NULL error word");
+    MGN_REQUIRE(num_edges != nullptr && col_ptr != nullptr && row_ptr != nullptr, who + ": a null pointer argument");
+    MGN_REQUIRE(ws_bytes >= mgn_world_topology_workspace_bytes(N, W), who + ": workspace too small");
+    if (N == 0) return 0;
+    MGN_REQUIRE(B >= 1, who + ": nodes without a graph (B == 0)");
+    MGN_REQUIRE(pos && node_type && graph_ptr && mesh_ptr && (mesh_nbr || E_m == 0) && csc_src && csc_dst &&
+                    csc_eid && row_perm && edge_index && ws,
+                who + ": a null pointer argument");
+    hipStream_t st = (hipStream_t)stream;
+    char* w = reinterpret_cast<char*>(ws);
+    int32_t* wc = reinterpret_cast<int32_t*>(w); w += al((size_t)N * 4);
+    int32_t* wl = reinterpret_cast<int32_t*>(w);
+    const int n = (int)N, e_m = (int)E_m, e_cap = (int)(E_m + N * (int64_t)W);
+    hipLaunchKernelGGL(world_search, dim3((unsigned)cdiv64(N, WORLD_THREADS)), dim3(WORLD_THREADS), 0, st, pos, ld_pos,
+                       node_type, ld_type, graph_ptr, (int)B, n, mesh_ptr, mesh_nbr, e_m, radius * radius, (int)W, wl,
+                       wc, err_word);
+    MGN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(world_scan, dim3(1), dim3(WORLD_SCAN_THREADS), 0, st, mesh_ptr, e_m, wc, n, e_cap, col_ptr,
+                       row_ptr, num_edges);
+    MGN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(world_merge, dim3((unsigned)cdiv64(N * WORLD_MERGE_LANES, 256)), dim3(256), 0, st, mesh_ptr,
+                       mesh_nbr, e_m, wl, wc, (int)W, n, e_cap, col_ptr, csc_src, csc_dst, csc_eid, row_perm,
+                       edge_index, err_word);
+    MGN_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"

@@ -199,6 +199,9 @@ EXPORTS = {
     "mgn_feed_batch_world": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _i32, FeedRanges, _vp, _vp,
                                     _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "mgn_feed_world_edge_features": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp]),
+    "mgn_world_topology_workspace_bytes": (_sz, [_i64, _i32]),
+    "mgn_world_topology_build": (_i32, [_vp, _i64, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _i64, _dbl, _i32, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mgn_feed_inflow_capacity": (_i32, []),
     "mgn_feed_inflow_stats": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp]),
     "mgn_feed_batch_aneurysm": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, FeedRanges8,
@@ -293,6 +296,7 @@ def check(rc):
 # ---------------------------------------------------------------- device error word (ABI v7)
 ERR_EDGE_INDEX, ERR_TYPE_NEG, ERR_TYPE_BIG = 1, 2, 4
 ERR_HANDOFF = 8  # ABI v17: a pipelined kernel's bounded hand-off wait timed out (mgn.h MGN_ERR_HANDOFF)
+ERR_WORLD_CAPACITY = 16  # mgn.h MGN_ERR_WORLD_CAPACITY: a node with more world neighbours than max_neighbors
 ERR_ANY, ERR_SKIP_SHIFT, ERR_STALE = 0xFFFF, 16, 1 << 31  # ABI v11 (include/mgn.h)
 
 
@@ -313,9 +317,18 @@ def _raise_for(bits):
         # gave up waiting inside its pipeline and wrote NaN partial sums; the optimizer step was skipped
         ex = RuntimeError("libmgn: a hand-off wait of the recomputed weight gradients timed out "
                           "(MGN_ERR_HANDOFF); the step's gradients are invalid and its optimizer update was skipped")
+    elif bits & ERR_WORLD_CAPACITY:
+        ex = world_capacity_error()
     if ex is not None:
         ex.mgn_skipped_updates = (bits >> ERR_SKIP_SHIFT) & 0xFF
         raise ex
+
+
+def world_capacity_error():
+    """The ValueError of MGN_ERR_WORLD_CAPACITY (the device check of mgn_world_topology_build, and the host check
+    of dataset.resident.world_topology_torch)."""
+    return ValueError("dynamic_edges: a node has more world neighbours within the radius than max_neighbors; the "
+                      "step's topology is invalid and its optimizer update was skipped: raise max_neighbors")
 
 
 class ErrorWord:
@@ -658,6 +671,63 @@ def feed_world_edge_features(senders, receivers, x, edge_attr, start):
                              "device with unit column stride")
     check(lib().mgn_feed_world_edge_features(ptr(senders), ptr(receivers), E, ptr(x), x.stride(0), ptr(edge_attr),
                                              edge_attr.stride(0), int(start), stream_ptr(x.device)))
+
+
+def world_topology_workspace(N, max_neighbors, device):
+    """The scratch of one mgn_world_topology_build over N nodes (uint8, caller-kept)."""
+    import torch
+
+    return torch.empty(max(int(lib().mgn_world_topology_workspace_bytes(int(N), int(max_neighbors))), 1),
+                       dtype=torch.uint8, device=device)
+
+
+def world_topology_build(pos, node_type, graph_ptr, mesh_ptr, mesh_nbr, radius, max_neighbors, csc_src, csc_dst,
+                         csc_eid, col_ptr, row_ptr, row_perm, edge_index, num_edges, ws):
+    """The topology of mesh edges ∪ OBSTACLE–NORMAL pairs within `radius`, per graph (mgn_world_topology_build):
+    pos fp32 [N, >= 3] with unit column stride, node_type an fp32 [N] view of any stride (a column of x), graph_ptr
+    int32 [B + 1], mesh_ptr int32 [N + 1] / mesh_nbr int32 [E_m] the static adjacency as CSR. Writes the six arrays
+    ([E_cap] and [N + 1] int32, E_cap = E_m + N · max_neighbors), edge_index int64 [2, E_cap] and num_edges int32
+    [1] in place on the current stream; a node over capacity flags the device error word (ValueError at the next
+    poll). Nothing is read back."""
+    import torch
+
+    require_device(pos)
+    dev, N, E_m, W = pos.device, pos.shape[0], mesh_nbr.numel(), int(max_neighbors)
+    if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] < 3 or pos.stride(1) != 1:
+        raise ValueError("world_topology_build: pos must be an fp32 [N, >= 3] tensor with unit column stride")
+    t = node_type
+    if t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != N or t.device != dev or (N > 1 and t.stride(0) < 1):
+        raise ValueError(f"world_topology_build: node_type must be an fp32 [{N}] tensor (a view of any positive "
+                         "stride) on pos's device")
+    if W < 1:
+        raise ValueError(f"world_topology_build: max_neighbors {W} must be >= 1")
+    if not float(radius) > 0.0 or float(radius) == float("inf"):
+        raise ValueError(f"world_topology_build: radius {radius} must be positive and finite")
+    E_cap = E_m + N * W
+    for name, a, n in (("graph_ptr", graph_ptr, None), ("mesh_ptr", mesh_ptr, N + 1), ("mesh_nbr", mesh_nbr, E_m),
+                       ("csc_src", csc_src, max(E_cap, 1)), ("csc_dst", csc_dst, max(E_cap, 1)),
+                       ("csc_eid", csc_eid, max(E_cap, 1)), ("row_perm", row_perm, max(E_cap, 1)),
+                       ("col_ptr", col_ptr, N + 1), ("row_ptr", row_ptr, N + 1), ("num_edges", num_edges, 1)):
+        if a.dtype != torch.int32 or a.dim() != 1 or not a.is_contiguous() or a.device != dev or \
+                (n is not None and a.numel() != n):
+            raise ValueError(f"world_topology_build: {name} must be a contiguous int32 "
+                             f"[{'B + 1' if n is None else n}] tensor on pos's device")
+    if graph_ptr.numel() < 1 or (N > 0 and graph_ptr.numel() < 2):
+        raise ValueError("world_topology_build: graph_ptr must hold B + 1 node offsets")
+    ei = edge_index
+    if ei.dtype != torch.int64 or tuple(ei.shape) != (2, max(E_cap, 1)) or not ei.is_contiguous() or ei.device != dev:
+        raise ValueError(f"world_topology_build: edge_index must be a contiguous int64 [2, {max(E_cap, 1)}] tensor on "
+                         "pos's device")
+    wsb = int(lib().mgn_world_topology_workspace_bytes(N, W))
+    if ws.dtype != torch.uint8 or ws.numel() < wsb or ws.device != dev:
+        raise ValueError(f"world_topology_build: ws must hold {wsb} bytes on pos's device")
+    ew = error_word(dev)
+    check(lib().mgn_world_topology_build(
+        ptr(pos), pos.stride(0) if N > 1 else max(pos.stride(0), 3), ptr(t), t.stride(0) if N > 1 else 1,
+        ptr(graph_ptr), graph_ptr.numel() - 1, N, ptr(mesh_ptr), ptr(mesh_nbr), E_m, float(radius), W, ptr(csc_src),
+        ptr(csc_dst), ptr(csc_eid), ptr(col_ptr), ptr(row_ptr), ptr(row_perm), ptr(ei), ptr(num_edges), ew.ptr(),
+        ptr(ws), ws.numel(), stream_ptr(dev)))
+    ew.arm()
 
 
 def feed_ranges8(ranges):

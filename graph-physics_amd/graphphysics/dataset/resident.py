@@ -36,12 +36,21 @@ ascending order) and picked by the fill, mgn_feed_batch_aneurysm, one launch wit
 columns (up to 8 ranges here: the configs have six). inflow_stats_torch / fill_aneurysm_torch state both rules;
 graphphysics.external.aneurysm.build_features is the per-item transform on the same rules.
 
-Not supported: `previous_data` outside aneurysm= (there it is the frame before the drawn one), world edges that
-change from frame to frame (the edge_index given with world_pos= is static for the life of the feed: the radius
-search is not part of the fill), rotate= together with world_pos=, aneurysm= together with either, a wall flag
-that changes over time (aneurysm= takes the node types from frame 0), and trajectories of unequal length in one
-batch. batch.edge_index is never touched, batch.edge_attr only by a rotating feed that was given a clean edge_attr
-and by a world_pos= feed that was given an edge_index.
+World edges that change from frame to frame (dynamic_edges=, with world_pos=; the reference's add_world_edges,
+dataset/preprocessing.py:92-140, which build_preprocessing runs per item after the noise, and which is the only path
+from the obstacle to the plate in a transformer config such as plate.json, whose attention is masked by the
+adjacency): after the fill and the noise, mgn_world_topology_build finds every graph's OBSTACLE–NORMAL pairs within
+the radius from the noisy x, merges them into the static mesh adjacency and rewrites, in place and without the host,
+the six arrays of the feed's topology, its edge_index and its edge count. batch.edge_index is the feed's own tensor,
+bound to that topology (models._engine.bind_topology), so a recorded step keeps reading the same addresses and every
+replay attends over the contacts of its own batch. world_topology_torch states the rule.
+
+Not supported: `previous_data` outside aneurysm= (there it is the frame before the drawn one), dynamic_edges= for
+models with edge_attr (the MGN path: its launch shapes depend on the edge count; the edge_index given inside
+world_pos= stays static for the life of the feed), rotate= together with world_pos=, aneurysm= together with either,
+a wall flag that changes over time (aneurysm= takes the node types from frame 0), and trajectories of unequal length
+in one batch. batch.edge_index is written only by a dynamic_edges= feed (through its own tensor), batch.edge_attr
+only by a rotating feed that was given a clean edge_attr and by a world_pos= feed that was given an edge_index.
 
 The validation rollout reads the same resident frames (training.rollout.Rollout.rollout_resident):
 rollout_begin_torch / rollout_end_torch state, as torch ops on any device, the two rules libmgn's
@@ -282,6 +291,85 @@ def world_edge_features_torch(x, edge_index, edge_attr, start):
     return edge_attr
 
 
+def check_mesh_edges(edge_index, graph_ptr, N):
+    """The host-side preconditions of a dynamic_edges mesh (ValueError): an integer [2, E_m] tensor with node ids in
+    [0, N), sorted by (row, col), without duplicates or self-loops, symmetric, every edge inside one graph — what
+    FaceToEdge + to_undirected emit for a batch. Returns it as int64 on the CPU."""
+    ei = edge_index
+    if not torch.is_tensor(ei) or ei.dim() != 2 or ei.shape[0] != 2 or ei.is_floating_point() or ei.dtype == torch.bool:
+        raise ValueError("dynamic_edges edge_index must be an integer [2, E] tensor")
+    ei = ei.to("cpu", torch.int64).contiguous()
+    if ei.shape[1] == 0:
+        return ei
+    if int(ei.min()) < 0 or int(ei.max()) >= N:
+        raise ValueError(f"dynamic_edges edge_index holds node ids outside [0, {N})")
+    if bool((ei[0] == ei[1]).any()):
+        raise ValueError(f"dynamic_edges edge_index holds a self-loop (edge {int(torch.nonzero(ei[0] == ei[1])[0])})")
+    key = ei[0] * N + ei[1]
+    if bool((key[1:] <= key[:-1]).any()):
+        bad = int(torch.nonzero(key[1:] <= key[:-1])[0]) + 1
+        what = "a duplicate" if int(key[bad]) == int(key[bad - 1]) else "not sorted by (row, col)"
+        raise ValueError(f"dynamic_edges edge_index must be sorted by (row, col) and unique: edge {bad} is {what}")
+    back = ei[1] * N + ei[0]
+    if not torch.equal(torch.sort(back).values, key):
+        raise ValueError("dynamic_edges edge_index must be symmetric: an edge has no reverse edge")
+    node_graph = _node_graph(graph_ptr, N, "cpu")
+    cross = node_graph[ei[0]] != node_graph[ei[1]]
+    if bool(cross.any()):
+        raise ValueError(f"dynamic_edges edge {int(torch.nonzero(cross)[0])} joins nodes of different graphs")
+    return ei
+
+
+def world_topology_torch(pos, node_type, graph_ptr, mesh_edge_index, radius, max_neighbors=None):
+    """mgn_world_topology_build's rule as torch ops on any device — the reference's add_world_edges
+    (dataset/preprocessing.py:92-140) applied to every graph of the batch on its own, then batched. Nodes i, j of one
+    graph are linked when one is NORMAL, the other OBSTACLE, and the squared distance of their fp32 positions
+    pos[:, 0:3], taken in fp64 as (v0·v0 + v1·v1) + v2·v2 with v the fp64 difference, is <= radius·radius (cKDTree's
+    verdict); the result is the union of the mesh edges (check_mesh_edges' preconditions) and both directions of
+    every pair, sorted by (row, col), every edge once. Returns (edge_index int64 [2, E], arrays): arrays is a dict of
+    the six int32 tensors csc_src, csc_dst, csc_eid, row_perm [E] and col_ptr, row_ptr [N + 1] that
+    mgn_topology_build gives for that edge_index, derived as the kernel derives them — the adjacency is symmetric, so
+    the target-sorted list is the (row, col)-sorted one with its rows swapped, and an edge's place in the other order
+    is the rank of its reverse. max_neighbors: a node with more world neighbours (pairs that are not mesh edges)
+    raises the ValueError of MGN_ERR_WORLD_CAPACITY. What a dynamic_edges= feed runs on CPU tensors, and what the
+    kernels are tested against."""
+    dev, N = pos.device, pos.shape[0]
+    gp = [int(v) for v in (graph_ptr.tolist() if torch.is_tensor(graph_ptr) else graph_ptr)]
+    mesh = mesh_edge_index.to(dev, torch.int64)
+    p, t, r2 = pos[:, 0:3].double(), node_type.to(dev), float(radius) * float(radius)
+    wi, wj = [], []
+    for a, b in zip(gp, gp[1:]):
+        if b <= a:
+            continue
+        v = p[a:b, None, :] - p[None, a:b, :]
+        d2 = (v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2]
+        normal, obstacle = t[a:b] == NodeType.NORMAL, t[a:b] == NodeType.OBSTACLE
+        pair = (normal[:, None] & obstacle[None, :]) | (obstacle[:, None] & normal[None, :])
+        i, j = torch.nonzero(pair & (d2 <= r2), as_tuple=True)
+        wi.append(i + a)
+        wj.append(j + a)
+    mesh_key = mesh[0] * N + mesh[1]
+    if wi:
+        world_key = torch.cat(wi) * N + torch.cat(wj)
+        world_key = world_key[~torch.isin(world_key, mesh_key)]  # already a mesh edge: to_undirected keeps one
+    else:
+        world_key = mesh_key[:0]
+    if max_neighbors is not None and world_key.numel() and \
+            int(torch.bincount(torch.div(world_key, max(N, 1), rounding_mode="floor")).max()) > int(max_neighbors):
+        raise nat.world_capacity_error()
+    key = torch.sort(torch.cat([mesh_key, world_key])).values
+    row, col = torch.div(key, max(N, 1), rounding_mode="floor"), key % max(N, 1)
+    ptr = torch.searchsorted(row.contiguous(), torch.arange(N + 1, device=dev)).to(torch.int32)
+    # target-sorted position k holds edge (src = col[k] → dst = row[k]); its id in (row, col) order is the rank of
+    # the reversed pair, and row_perm is that permutation's inverse
+    eid = torch.searchsorted(key, col * N + row)
+    perm = torch.empty_like(eid)
+    perm[eid] = torch.arange(eid.numel(), device=dev)
+    arrays = {"csc_src": col.to(torch.int32), "csc_dst": row.to(torch.int32), "csc_eid": eid.to(torch.int32),
+              "row_perm": perm.to(torch.int32), "col_ptr": ptr, "row_ptr": ptr.clone()}
+    return torch.stack([row, col]), arrays
+
+
 def check_rollout_columns(F, y_columns, out_columns, prev_columns, node_type_index):
     """The host-side preconditions of a resident rollout (ValueError): the model's output columns, the target
     columns and, when used, the previous-data columns have one width d; the output and previous-data ranges
@@ -433,8 +521,8 @@ class ResidentTrajectories:
 
     frame [B] int32, z [N, W] fp32 (None without noise) and scales [n] fp32 (None without noise) are
     allocated once and only rewritten: a captured graph keeps reading the same addresses, tests and users
-    read there what the last fill used. Not supported: previous_data (except with aneurysm=, below), per-frame
-    world edges, trajectories of unequal length (module docstring).
+    read there what the last fill used. Not supported: previous_data (except with aneurysm=, below), trajectories
+    of unequal length (module docstring).
 
     rotate: None, or the rotation augmentation of the reference's Random3DRotate, one rotation per graph and
     fill, as a dict
@@ -462,6 +550,22 @@ class ResidentTrajectories:
     With an edge side fill writes batch.edge_attr[:, edge_attr_start : edge_attr_start + 4] from the noisy x and
     touches no other column (the mesh's Cartesian ‖ Distance columns stay). Not together with rotate=.
 
+    dynamic_edges: None, or per-fill world edges for a model without edge_attr, with world_pos= (without its
+    edge_index / edge_attr_start), as a dict
+      {"edge_index": mesh_ei,    # [2, E_m]: the whole batch's block-diagonal mesh edges as FaceToEdge + to_undirected
+                                 # emit them: sorted by (row, col), unique, symmetric, no self-loops, no edge across
+                                 # two graphs — checked once here (check_mesh_edges)
+       "radius": 0.03,           # the reference's add_world_edges radius
+       "max_neighbors": 16}      # capacity: the most world neighbours one node may have
+    The feed then owns topology (models._engine.DynamicTopology; None on CPU tensors), edge_index (int64 [2, E_cap],
+    E_cap = E_m + N · max_neighbors: the tensor the caller puts into batch.edge_index; its first num_edges columns are
+    the reference's edge_index of the last fill, the rest is unspecified) and num_edges_dev (int32 [1]). fill rebuilds
+    them after the noise from batch.x[:, 0:3] and the batch's node-type column, as the reference's add_world_edges
+    reads them. A node with more than max_neighbors world neighbours is an error: on the device the step's optimizer
+    update is skipped and the next poll raises ValueError (MGN_ERR_WORLD_CAPACITY), on CPU tensors fill raises at
+    once. Node types are those of frame 0, as world_pos= assumes. Not together with rotate= or aneurysm=. Its
+    validation rollout: Rollout(..., feed=, world_edges="frame" | "prediction").
+
     aneurysm: None, or {"pos": pos} — pos fp32 [N, 3] on the feed's device, static and only read — for the row of
     the reference's external/aneurysm.py build_features. Frame rows are [velocity (3), wall flag (column 3), ...],
     F >= 4, T >= 3. The batch row is F + 10 wide, [frame row ‖ a − p ‖ pos ‖ mean, min, max ‖ node type], so
@@ -477,9 +581,10 @@ class ResidentTrajectories:
     ROTATE_KEYS = ("feature_indices", "edge_attr", "edge_index", "edge_feature_indices")
     WORLD_KEYS = ("world_pos_index_start", "world_pos_index_end", "node_type_index", "edge_index", "edge_attr_start")
     ANEURYSM_KEYS = ("pos",)
+    DYNAMIC_KEYS = ("edge_index", "radius", "max_neighbors")
 
     def __init__(self, traj, graph_ptr, y_columns, node_type_index, noise=None, frames="random", rotate=None,
-                 world_pos=None, aneurysm=None):
+                 world_pos=None, aneurysm=None, dynamic_edges=None):
         if not torch.is_tensor(traj) or traj.dtype != torch.float32 or traj.dim() != 3 or not traj.is_contiguous():
             raise ValueError("traj must be a contiguous fp32 [T, N, F] tensor")
         T, N, F = traj.shape
@@ -502,6 +607,11 @@ class ResidentTrajectories:
                                  f"{F + 9} (the last column of the row build_features makes)")
         elif not 0 <= int(node_type_index) < F:
             raise ValueError(f"node_type_index {node_type_index} is outside [0, {F})")
+        if dynamic_edges is not None:
+            if rotate is not None or aneurysm is not None:
+                raise ValueError("dynamic_edges= together with rotate= or aneurysm= is not supported")
+            if world_pos is None:
+                raise ValueError("dynamic_edges= needs world_pos=: the world edges follow the world positions")
         self.traj, self.T, self.N, self.F, self.B = traj, T, N, F, len(gp) - 1
         self.y_columns, self.node_type_index = (ys, ye), int(node_type_index)
         dev = traj.device
@@ -514,6 +624,11 @@ class ResidentTrajectories:
             if rotate is not None:
                 raise ValueError("rotate= together with world_pos= is not supported")
             self._init_world(world_pos, gp)
+        # dynamic_edges=: the world edges of every fill, as a topology rebuilt in place (see build_edges)
+        self.dynamic = dynamic_edges is not None
+        self.topology, self.edge_index, self.num_edges_dev, self.topology_arrays = None, None, None, None
+        if self.dynamic:
+            self._init_dynamic(dynamic_edges, gp)
         self.pos, self.node_type, self.inflow_stats, self.inflow_ptr, self.inflow_rows = None, None, None, None, None
         if self.aneurysm:
             self._init_aneurysm(aneurysm, gp)
@@ -587,6 +702,57 @@ class ResidentTrajectories:
             self.senders, self.receivers = ei[0].to(torch.int32).contiguous(), ei[1].to(torch.int32).contiguous()
             self.edge_attr_start, self._world_edge_index = int(start), ei
         self.obstacle_mean = torch.zeros(self.B, 3, dtype=torch.float32, device=dev)
+
+    def _init_dynamic(self, de, gp):
+        if not isinstance(de, dict) or any(k not in self.DYNAMIC_KEYS for k in de) or \
+                any(k not in de for k in self.DYNAMIC_KEYS):
+            raise ValueError(f"dynamic_edges must be a dict with the keys {self.DYNAMIC_KEYS}, got {de!r}")
+        if self.senders is not None:
+            raise ValueError("dynamic_edges= needs a world_pos= without edge_index / edge_attr_start: models with "
+                             "edge_attr are not supported (their launch shapes depend on the edge count)")
+        radius, W = de["radius"], de["max_neighbors"]
+        if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not 0.0 < float(radius) < math.inf:
+            raise ValueError(f"dynamic_edges radius {radius!r} must be a positive finite number")
+        if isinstance(W, bool) or not isinstance(W, int) or W < 1:
+            raise ValueError(f"dynamic_edges max_neighbors {W!r} must be an int >= 1")
+        dev, N = self.traj.device, self.N
+        mesh = check_mesh_edges(de["edge_index"], gp, N)
+        E_cap = mesh.shape[1] + N * W
+        if E_cap > 2 ** 31 - 1:
+            raise ValueError(f"dynamic_edges: E_m + N * max_neighbors = {E_cap} does not fit int32")
+        self.radius, self.max_neighbors, self._gp_list = float(radius), W, gp
+        self.mesh_edge_index = mesh.to(dev)
+        if dev.type == "cuda":
+            from graphphysics.models import _engine
+
+            self.topology = _engine.DynamicTopology(mesh, gp, N, self.radius, W, dev)
+            self.edge_index, self.num_edges_dev = self.topology.edge_index, self.topology.num_edges_dev
+            _engine.bind_topology(self.edge_index, self.topology)
+        else:
+            self.edge_index = torch.zeros(2, max(E_cap, 1), dtype=torch.int64)
+            self.num_edges_dev = torch.zeros(1, dtype=torch.int32)
+
+    def build_edges(self, pos, node_type):
+        """Rebuild the world edges from pos fp32 [N, >= 3] and node_type fp32 [N] (views of the batch's x): HIP
+        tensors, mgn_world_topology_build into self.topology (device work only, capturable); CPU tensors,
+        world_topology_torch into edge_index[:, :E], num_edges_dev and topology_arrays (a node over max_neighbors
+        raises at once there; on the device it flags the error word)."""
+        if not self.dynamic:
+            raise ValueError("build_edges: this feed was built without dynamic_edges=")
+        if pos.is_cuda:
+            self.topology.build(pos, node_type)
+            return
+        ei, arrays = world_topology_torch(pos, node_type, self._gp_list, self.mesh_edge_index, self.radius,
+                                          self.max_neighbors)
+        self.edge_index[:, :ei.shape[1]] = ei
+        self.num_edges_dev.fill_(ei.shape[1])
+        self.topology_arrays = arrays
+
+    def current_edge_index(self):
+        """edge_index[:, :num_edges] of the last build, a view (reads the count back: for CPU models and tests)."""
+        if not self.dynamic:
+            raise ValueError("current_edge_index: this feed was built without dynamic_edges=")
+        return self.edge_index[:, :int(self.num_edges_dev)]
 
     def _init_aneurysm(self, an, gp):
         if not isinstance(an, dict) or any(k not in self.ANEURYSM_KEYS for k in an) or "pos" not in an:
@@ -738,7 +904,9 @@ class ResidentTrajectories:
         mgn_feed_batch_world (two launches) in mgn_feed_batch's place and, with an edge side, one
         mgn_feed_world_edge_features into batch.edge_attr[:, start:start + 4]; CPU tensors: fill_world_torch and
         world_edge_features_torch. With aneurysm=: batch.x[:, :F + 10], one mgn_feed_batch_aneurysm in
-        mgn_feed_batch's place (the statistics table was built at construction); CPU tensors: fill_aneurysm_torch."""
+        mgn_feed_batch's place (the statistics table was built at construction); CPU tensors: fill_aneurysm_torch.
+        With dynamic_edges=: after the world fill, build_edges on the noisy x (mgn_world_topology_build, three
+        launches; CPU tensors: world_topology_torch), and batch.edge_index must be the feed's edge_index."""
         x, y = batch.x, batch.y
         if x.device != self.traj.device or x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != self.N or \
                 x.shape[1] < self.Fx:
@@ -764,6 +932,9 @@ class ResidentTrajectories:
                     wea.shape[0] != E or wea.shape[1] < A or wea.stride(1) != 1:
                 raise ValueError(f"batch.edge_attr must be fp32 [{E}, >= {A}] on {self.traj.device} with unit column "
                                  "stride")
+        if self.dynamic and x.is_cuda and getattr(batch, "edge_index", None) is not self.edge_index:
+            raise ValueError("with dynamic_edges=, batch.edge_index must be the feed's own edge_index tensor "
+                             "(feed.edge_index): it is the handle of the topology the fill rebuilds")
         with torch.no_grad():
             if self.random_frames:
                 # torch.randint(0, T-1, (B,)) into the persistent tensor; aneurysm=: frame t - 1 is read too
@@ -795,6 +966,8 @@ class ResidentTrajectories:
                     self.obstacle_mean.copy_(mean)
                     if wea is not None:
                         world_edge_features_torch(x, self._world_edge_index, wea, self.edge_attr_start)
+                if self.dynamic:  # add_world_edges reads the (noisy) world positions and the batch's node types
+                    self.build_edges(x, x[:, self.node_type_index + 3])
                 return batch
             if rot and self.random_rotations:
                 self.angles.uniform_(-math.pi, math.pi)  # one rotation per graph, as the reference's per item

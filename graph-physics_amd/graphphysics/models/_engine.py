@@ -2,6 +2,9 @@
 
 * GraphTopology  — target-sorted edge order + segment pointers for an edge_index (built on device
                    by mgn_topology_build, cached per edge_index tensor object).
+* DynamicTopology — the same arrays at a fixed capacity, rebuilt in place on the device from the step's positions
+                   (mesh edges ∪ per-frame world edges, mgn_world_topology_build); bind_topology ties it to the
+                   edge_index tensor that stands for it.
 * MlpSpec        — one build_mlp nn.Sequential (reference graphphysics/models/layers.py:77-113)
                    seen by the kernels: its Linear weights are packed into MFMA fragments, biases and
                    RMSNorm scale are read straight from the fp32 master parameters.
@@ -58,6 +61,53 @@ class GraphTopology:
         self.struct = nat.Topology(N, E, self.csc_src.data_ptr(), self.csc_dst.data_ptr(),
                                    self.csc_eid.data_ptr(), self.col_ptr.data_ptr(),
                                    self.row_ptr.data_ptr(), self.row_perm.data_ptr())
+
+
+class DynamicTopology:
+    """A topology whose world edges are rebuilt on the device, inside a recorded step (mgn_world_topology_build,
+    mgn.h "World edges inside the step"): the static mesh adjacency plus the OBSTACLE–NORMAL pairs of every graph
+    that lie within `radius`, found anew from the positions of every build. Same attributes and `struct` as
+    GraphTopology, over arrays of the fixed capacity E_cap = E_m + N · max_neighbors; num_edges is that capacity
+    (what workspaces are sized for), the live edge count is num_edges_dev (int32 [1], on the device) and
+    edge_index [2, E_cap] holds the reference's edge_index of the last build in its first num_edges_dev columns.
+    build() writes through raw pointers: no tensor here ever changes identity or _version, so
+    bind_topology(self.edge_index, self) keeps get_topology and every recorded graph on this object.
+
+    mesh_edge_index: int64 [2, E_m], sorted by (row, col), symmetric, unique, every edge inside one graph (the
+    caller validates it: dataset.resident.check_mesh_edges); graph_ptr: [B + 1] node offsets."""
+
+    def __init__(self, mesh_edge_index, graph_ptr, num_nodes, radius, max_neighbors, device):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("the MI355X MGN path needs tensors on a HIP device (no CPU fallback)")
+        N, W = int(num_nodes), int(max_neighbors)
+        ei = mesh_edge_index.to(torch.int64).cpu()
+        E_m = int(ei.shape[1])
+        E = E_m + N * W
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.num_nodes, self.num_edges, self.device = N, E, dev
+        self.num_mesh_edges, self.radius, self.max_neighbors = E_m, float(radius), W
+        self.mesh_ptr = torch.searchsorted(ei[0].contiguous(), torch.arange(N + 1)).to(**i32)
+        self.mesh_nbr = ei[1].to(**i32).contiguous()
+        self.graph_ptr = torch.as_tensor(graph_ptr).to(**i32).contiguous()
+        # zeros: an entry a build over capacity leaves unwritten is still a valid index (mgn.h, "Capacity")
+        self.csc_src, self.csc_dst = torch.zeros(max(E, 1), **i32), torch.zeros(max(E, 1), **i32)
+        self.csc_eid, self.row_perm = torch.zeros(max(E, 1), **i32), torch.zeros(max(E, 1), **i32)
+        self.col_ptr, self.row_ptr = torch.zeros(N + 1, **i32), torch.zeros(N + 1, **i32)
+        self.edge_index = torch.zeros(2, max(E, 1), dtype=torch.int64, device=dev)
+        self.num_edges_dev = torch.zeros(1, **i32)
+        self._ws = nat.world_topology_workspace(N, W, dev)
+        nat.error_word(dev)  # exists before any capture
+        self.struct = nat.Topology(N, E, self.csc_src.data_ptr(), self.csc_dst.data_ptr(),
+                                   self.csc_eid.data_ptr(), self.col_ptr.data_ptr(),
+                                   self.row_ptr.data_ptr(), self.row_perm.data_ptr())
+
+    def build(self, pos, node_type):
+        """Rebuild from pos fp32 [N, >= 3] (unit column stride; e.g. the batch's x) and node_type fp32 [N] (any
+        stride; e.g. a column of x): three launches on the current stream, capturable, nothing read back."""
+        nat.world_topology_build(pos, node_type, self.graph_ptr, self.mesh_ptr, self.mesh_nbr, self.radius,
+                                 self.max_neighbors, self.csc_src, self.csc_dst, self.csc_eid, self.col_ptr,
+                                 self.row_ptr, self.row_perm, self.edge_index, self.num_edges_dev, self._ws)
 
 
 # the block backward's weight-gradient halves run on a side stream, overlapped with the next block's
@@ -185,9 +235,29 @@ _TOPO_CACHE = []  # [(weakref(edge_index), version, num_nodes, topo)], most rece
 _TOPO_CACHE_MAX = 8
 
 
+_TOPO_BOUND = []  # [(weakref(edge_index), weakref(topo))]: bind_topology's pairs, never evicted while both live
+
+
+def bind_topology(edge_index, topo):
+    """Make get_topology(edge_index, topo.num_nodes) return `topo` for this exact tensor object for as long as both
+    live (weak references: the binding keeps neither alive). For a topology that is rebuilt in place on the device
+    (DynamicTopology): the tensor is a handle, its contents are not hashed and its _version is not looked at."""
+    _TOPO_BOUND[:] = [ent for ent in _TOPO_BOUND if ent[0]() is not None and ent[1]() is not None
+                      and ent[0]() is not edge_index]
+    _TOPO_BOUND.append((weakref.ref(edge_index), weakref.ref(topo)))
+
+
 def get_topology(edge_index, num_nodes):
     """Topology for this exact edge_index tensor object (identity + version checked: a freed
     tensor's address reused by a new one never hits a stale entry)."""
+    for ref, tref in _TOPO_BOUND:
+        if ref() is edge_index:
+            topo = tref()
+            if topo is not None:
+                if topo.num_nodes != num_nodes:
+                    raise ValueError(f"edge_index is bound to a topology of {topo.num_nodes} nodes, the batch has "
+                                     f"{num_nodes}")
+                return topo
     for i, (ref, ver, n, topo) in enumerate(_TOPO_CACHE):
         if ref() is edge_index and ver == edge_index._version and n == num_nodes:
             if i:

@@ -34,6 +34,13 @@ world positions of frame start + s (the reference's validation: its edge feature
 "prediction", the x the model is about to see, so from step 1 on the fed-back positions; "off", x only (models
 without edge_attr, feeds without an edge side). The default None refuses such a feed.
 
+World edges that change from frame to frame (a feed built with dynamic_edges=, the transformer configs such as
+plate.json): the same modes say which positions the reference's add_world_edges reads — "frame", the clean world
+positions of frame start + s (the reference's validation: its edge_index is part of the dataset item), "prediction",
+the x the model is about to see — and one mgn_world_topology_build between the begin stage and the forward rebuilds
+the feed's bound topology in place, inside the recorded step. "off" is refused: there is no static adjacency to
+fall back to. batch.edge_index must be feed.edge_index; the steps' edge counts are kept in resident_num_edges.
+
 Aneurysm data (a feed built with aneurysm=): Rollout(..., acceleration=MODE) runs the same three stages with
 mgn_rollout_begin_aneurysm in front — the row [frame row (F) ‖ a − p ‖ pos ‖ mean, min, max ‖ node type] of the
 reference's external/aneurysm.py build_features at frame start + s, from clean values, then the feedback, as the
@@ -102,6 +109,7 @@ class Rollout:
         self._res = None  # rollout_resident's state (_Resident)
         self.resident_records = 0  # how many times rollout_resident recorded its graph
         self._res_sq, self._res_count = [], 0  # Σ (pred − target)² per resident run (device), and their elements
+        self.resident_num_edges = None  # rollout_resident on a dynamic_edges= feed: the steps' edge counts
         if feed is not None:
             from graphphysics.dataset.resident import check_rollout_columns
 
@@ -186,7 +194,13 @@ class Rollout:
             if mode is not None:
                 raise ValueError(f"world_edges={mode!r} needs a feed built with world_pos=")
             return False
-        if mode != "off" and feed.senders is None:
+        if getattr(feed, "dynamic", False):
+            # a dynamic_edges= feed: the topology is rebuilt every step, from the clean frame or from the x the
+            # model sees; there is no static adjacency to fall back to
+            if mode == "off":
+                raise ValueError('world_edges="off" does not go with a feed built with dynamic_edges=: its world '
+                                 'edges are rebuilt every step, from "frame" or from "prediction"')
+        elif mode != "off" and feed.senders is None:
             raise ValueError(f"world_edges={mode!r} needs a feed whose world_pos= has an edge_index and an "
                              'edge_attr_start; use "off" for a model without edge_attr')
         if self.k != feed.node_type_index + 3:
@@ -328,6 +342,9 @@ class Rollout:
             st.obstacle_mean = torch.zeros(feed.B, 3, dtype=torch.float32, device=dev)
             if self.world_edges == "frame":  # the clean world positions of the step's frame: the edges' input
                 st.world_clean = torch.zeros(feed.N, 3, dtype=torch.float32, device=dev)
+        st.num_edges = None
+        if getattr(feed, "dynamic", False):  # the edge count of every step's rebuilt topology
+            st.num_edges = torch.zeros(cap, dtype=torch.int32, device=dev)
         st.ws, st.graph, st.topo = None, None, None
         if dev.type == "cuda":
             from graphphysics import _native as nat
@@ -363,7 +380,14 @@ class Rollout:
             begin_world(feed.traj, feed.graph_ptr, feed.frame, st.cursor, feed.y_columns, feed.node_type_index,
                         (self.os, self.oe), self._prev_cols, st.last, st.last_prev, st.x, st.y, st.obstacle_mean,
                         st.world_clean)
-            if mode != "off":  # "frame": the clean positions of the frame; "prediction": what the model sees
+            if getattr(feed, "dynamic", False):
+                # add_world_edges on the step's positions, between the begin stage and the forward: the bound
+                # topology is rewritten in place, st.frame.edge_index is its handle (on the CPU: the live columns)
+                feed.build_edges(st.world_clean if mode == "frame" else st.x, st.x[:, self.k])
+                st.num_edges.index_copy_(0, st.cursor.to(torch.int64), feed.num_edges_dev)
+                if not st.x.is_cuda:
+                    st.frame.edge_index = feed.current_edge_index()
+            elif mode != "off":  # "frame": the clean positions of the frame; "prediction": what the model sees
                 pos = st.world_clean if mode == "frame" else st.x
                 if st.x.is_cuda:
                     nat.feed_world_edge_features(feed.senders, feed.receivers, pos, st.edge_attr,
@@ -429,7 +453,11 @@ class Rollout:
                              f"got {tuple(x.shape)} {x.dtype} on {x.device}")
         if y is None or y.device != x.device or y.dtype != torch.float32 or tuple(y.shape) != (feed.N, d):
             raise ValueError(f"batch.y must be fp32 [{feed.N}, {d}] on {feed.traj.device}")
-        if world and self.world_edges != "off":
+        dynamic = world and getattr(feed, "dynamic", False)
+        if dynamic and batch.edge_index is not feed.edge_index:
+            raise ValueError("with a dynamic_edges= feed, batch.edge_index must be the feed's own edge_index tensor "
+                             "(feed.edge_index): it is the handle of the topology the steps rebuild")
+        if world and self.world_edges != "off" and not dynamic:
             ea, E, A = getattr(batch, "edge_attr", None), feed.senders.numel(), feed.edge_attr_start + 4
             if ea is None or ea.device != x.device or ea.dtype != torch.float32 or ea.dim() != 2 or \
                     ea.shape[0] != E or ea.shape[1] < A or ea.stride(1) != 1:
@@ -464,6 +492,8 @@ class Rollout:
                 st.graph.replay()
             else:
                 self._resident_step(st)
+        # a dynamic_edges= feed: the edge count of every step's topology (device int32 [steps]); None otherwise
+        self.resident_num_edges = st.num_edges[:steps].clone() if st.num_edges is not None else None
         loss, sq = st.loss[:steps].clone(), st.sq[:steps].clone()
         self.losses.extend(loss.unbind(0))
         self._res_sq.append(sq)

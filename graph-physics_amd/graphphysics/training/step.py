@@ -154,6 +154,8 @@ class TrainStep:
         """A validation error of an earlier step surfaced (reference IndexError / RuntimeError): the
         device skipped every optimizer update since (mgn_adamw_dev predication), so rewind the
         host-side counters by as many. Every poll point of a step comes before its own stage()."""
+        if isinstance(ex, ValueError) and not hasattr(ex, "mgn_skipped_updates"):
+            return  # an argument check of the host, not a device validation error (the capacity of dynamic edges is)
         n = getattr(ex, "mgn_skipped_updates", 0)
         if n:
             self._rewind(n)
@@ -205,7 +207,7 @@ class TrainStep:
                 self.feed.fill(self.batch)
             self._prologue()
             loss = self._loss()  # the Simulator / topology build poll the error word too
-        except (IndexError, RuntimeError) as ex:
+        except (IndexError, RuntimeError, ValueError) as ex:
             self._raised(ex)
             raise
         loss.backward(self._seed(loss))
@@ -259,7 +261,7 @@ class TrainStep:
         # a validation error of an EARLIER step surfaces here with its real skipped-update count
         try:
             nat.check_errors(dev)
-        except (IndexError, RuntimeError) as ex:
+        except (IndexError, RuntimeError, ValueError) as ex:
             self._raised(ex)
             raise
         extra = {k: getattr(b, k) for k in ("pos",) if getattr(b, k, None) is not None}
@@ -280,7 +282,9 @@ class TrainStep:
             cur.wait_stream(side)
             torch.cuda.synchronize()
             nat.check_errors(dev)  # the warm-up steps validated THIS batch
-        except (IndexError, RuntimeError):
+        except (IndexError, RuntimeError, ValueError) as ex0:
+            if isinstance(ex0, ValueError) and not hasattr(ex0, "mgn_skipped_updates"):
+                raise  # an argument check of the host: nothing was flagged on the device
             # the batch is invalid: undo the warm-up steps (their skipped updates and normalizer
             # accumulations are not the caller's), then run ONE eager step on it — exactly what the
             # eager path does with a bad batch (the normalizers the reference runs before its raise
@@ -298,7 +302,7 @@ class TrainStep:
             torch.cuda.synchronize()
             try:
                 nat.check_errors(dev)
-            except (IndexError, RuntimeError) as ex2:
+            except (IndexError, RuntimeError, ValueError) as ex2:
                 self._raised(ex2)
                 raise
             raise RuntimeError("libmgn: validation error during graph warm-up did not reproduce eagerly")
@@ -397,7 +401,7 @@ class TrainStep:
         dev = self.batch.x.device
         try:
             nat.poll_errors(dev)
-        except (IndexError, RuntimeError) as ex:
+        except (IndexError, RuntimeError, ValueError) as ex:
             self._raised(ex)
             raise
         if self.graph is not None:

@@ -67,6 +67,8 @@ const char* mgn_last_error(void);
 #define MGN_ERR_HANDOFF 8u    /* ABI v17: a bounded hand-off wait inside a pipelined kernel (the recomputed
                                  weight gradients, mgn_block_backward_deferred3) timed out; the kernel
                                  wrote NaN into its partial sums instead of a partial result           */
+#define MGN_ERR_WORLD_CAPACITY 16u /* a node has more world neighbours than max_neighbors
+                                      (mgn_world_topology_build kept the smallest; the topology is unspecified)  */
 #define MGN_ERR_ANY 0xFFFFu   /* any validation error (bits 0-15)                                      */
 /* State updates are predicated on the word, so an error raised lazily (one call late) leaves the
  * training state as the reference's immediate exception would (ABI v11): mgn_adamw_dev skips its
@@ -611,8 +613,8 @@ int mgn_feed_rotate_rows(const float* src, int64_t rows, int32_t cols, int64_t l
  * N == 0, B == 0 and E == 0 return 0 without a launch. Before any launch, a nonzero status for everything
  * mgn_feed_batch refuses (ranges and ldx checked against F + 3), F < 4, type_index < 3 or >= F, y_start != 0,
  * y_end < 3, a noisy range containing batch column type_index + 3, obstacle_mean == NULL; for the edge features
- * ld_ea < start + 4, start < 0, ldx < 3, null pointers with E > 0. Not covered: world edges that change from
- * frame to frame (the edge list is static), previous_data, rotation together with world positions; the
+ * ld_ea < start + 4, start < 0, ldx < 3, null pointers with E > 0. Not covered: previous_data, rotation together
+ * with world positions; world edges that change from frame to frame are mgn_world_topology_build below; the
  * Lagrangian rollout is mgn_rollout_begin_world below. The added symbols do not change MGN_ABI_VERSION; MGN_HAS_FEED_WORLD marks headers that declare them. */
 #define MGN_HAS_FEED_WORLD 1
 int mgn_feed_batch_world(const float* traj, int64_t T, int64_t N, int32_t F, const int32_t* graph_ptr, int32_t B,
@@ -625,6 +627,54 @@ int mgn_feed_batch_world(const float* traj, int64_t T, int64_t N, int32_t F, con
 int mgn_feed_world_edge_features(const int32_t* senders /* device, [E] */, const int32_t* receivers /* device, [E] */,
                                  int64_t E, const float* x, int64_t ldx, float* edge_attr, int64_t ld_ea,
                                  int32_t start, mgn_stream_t stream);
+
+/* World edges inside the step (the reference's add_world_edges, dataset/preprocessing.py:92-140, which
+ * build_preprocessing runs per item after the noise: every sample gets its own OBSTACLE–NORMAL contact edges, and a
+ * transformer's attention is masked by them). One call builds, with no host read-back, the topology of
+ *     mesh edges  ∪  both directions of every world pair
+ * for a batch of graphs, each graph searched on its own.
+ *   Pair rule. Nodes i and j of the SAME graph (graph_ptr [B + 1] node offsets) are a pair when one has node type 0
+ *     (NORMAL), the other 1 (OBSTACLE) — node_type[r * ld_type], compared as floats — and
+ *         ((double) pos[i][0] - (double) pos[j][0])² + (…[1])² + (…[2])²  <=  radius * radius
+ *     in fp64, the squares added in dimension order, every product and sum rounded on its own: mgn_radius_pairs'
+ *     arithmetic, whose pairs are scipy cKDTree.query_pairs'. Nodes of different graphs are never paired (the
+ *     reference preprocesses before it batches). A pair that is already a mesh edge appears once (to_undirected).
+ *   Mesh. mesh_ptr [N + 1] / mesh_nbr [E_m]: the static adjacency as CSR, the neighbours of a node ascending, symmetric,
+ *     without duplicates, every edge inside one graph, mesh_ptr[0] = 0 and mesh_ptr[N] = E_m — what FaceToEdge +
+ *     to_undirected emit, read row by row. These are preconditions the caller validates once; a neighbour outside
+ *     [0, N) sets MGN_ERR_EDGE_INDEX and is clamped.
+ *   Result, with E = E_m + (number of directed world edges) and capacity E_cap = E_m + N * max_neighbors:
+ *     edge_index [2, E_cap] int64, rows E_cap apart: the first E columns are the reference's edge_index of the
+ *       batch, sorted by (row, col); columns at and beyond E are unspecified.
+ *     csc_src, csc_dst, csc_eid, row_perm [E_cap] and col_ptr, row_ptr [N + 1]: entry for entry what
+ *       mgn_topology_build gives for that edge_index — within a target's segment the sources ascend, row_ptr ==
+ *       col_ptr, row_perm[r] = the target-sorted position of the r-th edge in (row, col) order, csc_eid its inverse —
+ *       so every kernel that reads a mgn_topology sums in the same order as on a host-built one. Entries at and
+ *       beyond E are unspecified. A mgn_topology over these arrays carries num_edges = E_cap (workspace sizes).
+ *     *num_edges (device int32) = E = col_ptr[N].
+ *   Capacity. A node with more than max_neighbors world neighbours keeps its max_neighbors smallest and ORs
+ *     MGN_ERR_WORLD_CAPACITY into *err_word (inside MGN_ERR_ANY: mgn_adamw_dev skips the update). The topology's
+ *     contents are then unspecified, but every index this call writes lies inside its array and inside [0, N), and
+ *     col_ptr / row_ptr stay non-decreasing within [0, E_cap]; entries the call did not write keep their previous
+ *     values, so the caller initialises the six arrays and edge_index once (zeros) before the first build.
+ * Three launches (search: one thread per node, the candidates of its graph staged through LDS; one exclusive scan of
+ * the degrees; merge: eight lanes per node, two ascending lists merged, the rank in the source's lists by binary
+ * search). Every grid is a function of N alone; no allocation, no synchronisation, no float reduction, no sort:
+ * capturable, the same bits on every replay. ws: mgn_world_topology_workspace_bytes(N, max_neighbors), caller-owned.
+ * N == 0 returns 0 without a launch. Before any launch, a nonzero status for NULL pointers, max_neighbors < 1,
+ * radius <= 0 or not finite, ld_pos < 3, ld_type < 1, N > 0 with B == 0, N > 2^30, E_m + N * max_neighbors beyond int32, a
+ * workspace too small. The added symbols do not change MGN_ABI_VERSION; MGN_HAS_WORLD_TOPOLOGY marks headers that
+ * declare them. */
+#define MGN_HAS_WORLD_TOPOLOGY 1
+size_t mgn_world_topology_workspace_bytes(int64_t num_nodes, int32_t max_neighbors);
+int mgn_world_topology_build(const float* pos, int64_t ld_pos /* >= 3 */,
+                             const float* node_type, int64_t ld_type,   /* e.g. a column of the batch's x */
+                             const int32_t* graph_ptr, int32_t B, int64_t num_nodes,
+                             const int32_t* mesh_ptr, const int32_t* mesh_nbr, int64_t num_mesh_edges,
+                             double radius, int32_t max_neighbors,
+                             int32_t* csc_src, int32_t* csc_dst, int32_t* csc_eid, int32_t* col_ptr, int32_t* row_ptr,
+                             int32_t* row_perm, int64_t* edge_index, int32_t* num_edges /* device */,
+                             uint32_t* err_word, void* ws, size_t ws_bytes, mgn_stream_t stream);
 
 /* Aneurysm features inside the feed (the reference's external/aneurysm.py build_features, which train.py hard-wires
  * as extra_node_features, then add_noise; coarse-aneurysm.json is written for this row). Frame rows are
