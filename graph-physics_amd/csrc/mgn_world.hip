@@ -23,6 +23,24 @@
 //                  the edge's place in (row, col) order, which gives csc_eid, row_perm and both edge_index rows.
 // Brute force per graph is deliberate: contact sets are small, it needs no bounding box, no grid and no sort, and
 // the order of every list is fixed. Every grid is a function of N alone.
+//
+// Random long-range edges (mgn.h, "Random edges inside the step"; the reference's _add_random_edges,
+// dataset/dataset.py:104-137) reuse the scan and the merge: only the producer of the per-node lists differs.
+//   random_map     one thread per candidate c: the graph whose candidate range holds c (binary search) and the mapped
+//                  endpoints (a, b) = (lo_g + u % n_g, lo_g + v % n_g), so that the search loads plain pairs.
+//   random_search  pass 1, mapped like world_search: one thread per node i, 256 per workgroup. The candidates of the
+//                  graphs that own the workgroup's nodes are staged through LDS in tiles of RANDOM_TILE (loaded into
+//                  registers one tile ahead), each entry the mapped endpoints (a, b), 8 bytes, read by every lane at
+//                  the same address (a broadcast); one unsigned minimum over a ^ i and b ^ i per chunk of eight. The
+//                  candidates that touch i are queued per lane (in LDS) and walked, in order, at the end: one
+//                  that is no self-pair and no mesh edge (binary search) and whose other endpoint j is not yet in
+//                  the node's list (a linear look-up, the list holds at most 64) is appended to wl[i*W ..] with its
+//                  candidate id beside it in wid[i*W ..]; when the list is full the candidate is flagged instead
+//                  (flag[c] = 1, a plain store: both endpoints may write the same 1).
+//   random_filter  pass 2, one thread per node: the entries whose candidate is unflagged, insertion-sorted ascending
+//                  in place, and their count into wc[i]. A pair survives exactly when its first candidate is
+//                  unflagged, which both endpoints see alike, so the lists are symmetric, as world_merge needs.
+// No atomics, no read-back; the grids are functions of N and of the candidate count, both fixed at construction.
 #include "mgn_common.h"
 
 namespace {
@@ -209,6 +227,159 @@ __global__ __launch_bounds__(256) void world_merge(const int32_t* __restrict__ m
     if (bad) atomicOr(err, MGN_ERR_EDGE_INDEX);
 }
 
+constexpr int RANDOM_TILE = 1024;  // candidates per LDS tile: 8 KiB
+constexpr int RANDOM_CHUNK = 8;
+constexpr int RANDOM_QUEUE = 32;  // hits a lane queues before it walks them: at least 2 * RANDOM_CHUNK
+constexpr int RANDOM_MAX_NEW = 64;
+
+constexpr int RANDOM_STAGE = (RANDOM_TILE + RANDOM_CHUNK + WORLD_THREADS - 1) / WORLD_THREADS;  // entries a thread stages
+
+// mapped[c] = the endpoints (a, b) of candidate c: one thread per candidate. The graph whose candidate range holds c
+// is found by binary search; (-1, -1), which matches no node, for a graph without nodes. The draws are non-negative;
+// the mask keeps any other bits in range as well.
+__global__ __launch_bounds__(WORLD_THREADS) void random_map(const int32_t* __restrict__ pairs,
+                                                            const int32_t* __restrict__ cand_ptr, int C,
+                                                            const int32_t* __restrict__ graph_ptr, int B, int N,
+                                                            const int32_t* __restrict__ enabled,
+                                                            int2* __restrict__ mapped) {
+    const int c = blockIdx.x * WORLD_THREADS + threadIdx.x;
+    if (c >= C || *enabled == 0) return;  // switched off, the search reads no candidate
+    const int g = graph_of_row(cand_ptr, B, c);
+    const int lo = clampi(graph_ptr[g], 0, N);
+    const int n = clampi(graph_ptr[g + 1], lo, N) - lo;
+    int2 e = make_int2(-1, -1);
+    if (n > 0) {
+        const int u = pairs[2 * (int64_t)c] & 0x7fffffff, v = pairs[2 * (int64_t)c + 1] & 0x7fffffff;
+        e = make_int2(lo + u % n, lo + v % n);
+    }
+    mapped[c] = e;
+}
+
+__global__ __launch_bounds__(WORLD_THREADS) void random_search(
+    const int2* __restrict__ mapped, const int32_t* __restrict__ cand_ptr, int C,
+    const int32_t* __restrict__ graph_ptr, int B, int N, const int32_t* __restrict__ mesh_ptr,
+    const int32_t* __restrict__ mesh_nbr, int E_m, int W, const int32_t* __restrict__ enabled, int32_t* wl,
+    int32_t* wid, int32_t* __restrict__ wc, int32_t* __restrict__ flag) {
+    // the mapped endpoints (a, b) of a tile; (-1, -1) behind its end, so that a chunk may be read whole
+    __shared__ int2 cand[RANDOM_TILE + RANDOM_CHUNK];
+    __shared__ int32_t queue[RANDOM_QUEUE][WORLD_THREADS];  // per lane: the candidates that touch its node
+    const int b0 = blockIdx.x * WORLD_THREADS;
+    const int b1 = min(N, b0 + WORLD_THREADS);  // b0 < N: the grid is cdiv(N, 256)
+    const int i = b0 + threadIdx.x;
+    const bool active = i < N;
+    // the candidates of every graph that owns one of this workgroup's nodes: uniform over the workgroup. Switched
+    // off (the device word is 0), the range is empty and every list stays empty
+    int c0 = 0, c1 = 0;
+    if (*enabled != 0) {
+        c0 = clampi(cand_ptr[graph_of_row(graph_ptr, B, b0)], 0, C);
+        c1 = clampi(cand_ptr[graph_of_row(graph_ptr, B, b1 - 1) + 1], c0, C);
+    }
+    int q0 = 0, q1 = 0, m0 = 0, md = 0;
+    if (active) {
+        const int g = graph_of_row(graph_ptr, B, i);
+        q0 = clampi(cand_ptr[g], c0, c1);
+        q1 = clampi(cand_ptr[g + 1], q0, c1);
+        m0 = clampi(mesh_ptr[i], 0, E_m);
+        md = clampi(mesh_ptr[i + 1], m0, E_m) - m0;
+    }
+    int32_t* mine = wl + (int64_t)i * W;
+    int32_t* mine_id = wid + (int64_t)i * W;
+    int cnt = 0, qn = 0;
+    // Pass 1 on this lane's queued hits, in candidate order. A hit costs a chain of dependent global loads (the
+    // mesh's binary search, the look-up in the node's own list), and a wave that handled every hit where it found
+    // it would pay that chain once per hit of any of its lanes, one after the other; queued, the lanes walk their
+    // own hits side by side: once at the end, and before that only for a lane whose queue is nearly full
+    auto drain = [&]() {
+        for (int s = 0; s < qn; ++s) {
+            const int c = queue[s][threadIdx.x];
+            const int2 q = mapped[c];
+            if (q.x == q.y) continue;  // a self-pair
+            const int j = q.x == i ? q.y : q.x;
+            const int at = lower_bound_i32(mesh_nbr + m0, md, j);
+            if (at < md && mesh_nbr[m0 + at] == j) continue;  // a mesh edge already
+            bool seen = false;
+            for (int k = 0; k < cnt; ++k) seen = seen || mine[k] == j;
+            if (seen) continue;  // a repeat
+            if (cnt == W) {
+                flag[c] = 1;  // dropped: pass 2 removes it at the other endpoint as well
+            } else {
+                mine[cnt] = j;
+                mine_id[cnt] = c;
+                ++cnt;
+            }
+        }
+        qn = 0;
+    };
+    // a tile's entries are loaded into registers one tile ahead, before the scan of the tile in LDS, so that the scan
+    // hides their latency
+    int2 next[RANDOM_STAGE];
+    auto fetch = [&](int t0) {
+#pragma unroll
+        for (int k = 0; k < RANDOM_STAGE; ++k) {
+            const int c = threadIdx.x + k * WORLD_THREADS;
+            next[k] = c < RANDOM_TILE && t0 + c < c1 ? mapped[t0 + c] : make_int2(-1, -1);
+        }
+    };
+    fetch(c0);
+    for (int t0 = c0; t0 < c1; t0 += RANDOM_TILE) {
+        const int nc = min(RANDOM_TILE, c1 - t0);
+#pragma unroll
+        for (int k = 0; k < RANDOM_STAGE; ++k) {
+            const int c = threadIdx.x + k * WORLD_THREADS;
+            if (c < RANDOM_TILE + RANDOM_CHUNK) cand[c] = next[k];
+        }
+        fetch(t0 + RANDOM_TILE);
+        __syncthreads();
+        if (active) {
+            // the node's own graph within the tile, from a chunk boundary on: the candidates ahead of lo and behind
+            // hi are other graphs' (their endpoints are other graphs' nodes) or the padding, and match no i
+            const int lo = max(q0, t0) - t0, hi = min(q1, t0 + nc) - t0;
+            // RANDOM_CHUNK candidates at a time: their LDS reads are issued together, and one unsigned minimum over
+            // a ^ i and b ^ i says whether any of them touches i (three VALU operations a candidate, no branch)
+            for (int c = lo & ~(RANDOM_CHUNK - 1); c < hi; c += RANDOM_CHUNK) {
+                int2 q[RANDOM_CHUNK];
+#pragma unroll
+                for (int u = 0; u < RANDOM_CHUNK; ++u) q[u] = cand[c + u];
+                unsigned none = ~0u;
+#pragma unroll
+                for (int u = 0; u < RANDOM_CHUNK; ++u)
+                    none = min(none, min((unsigned)(q[u].x ^ i), (unsigned)(q[u].y ^ i)));
+                if (none != 0u) continue;
+#pragma unroll
+                for (int u = 0; u < RANDOM_CHUNK; ++u)
+                    if (c + u >= lo && c + u < hi && (q[u].x == i || q[u].y == i)) queue[qn++][threadIdx.x] = t0 + c + u;
+                if (qn > RANDOM_QUEUE - RANDOM_CHUNK) drain();  // room for the next chunk's hits
+            }
+        }
+        __syncthreads();
+    }
+    if (active) {
+        drain();
+        wc[i] = cnt;
+    }
+}
+
+__global__ __launch_bounds__(WORLD_THREADS) void random_filter(int N, int W, int C, int32_t* wl,
+                                                               const int32_t* __restrict__ wid,
+                                                               int32_t* __restrict__ wc,
+                                                               const int32_t* __restrict__ flag) {
+    const int i = blockIdx.x * WORLD_THREADS + threadIdx.x;
+    if (i >= N) return;
+    int32_t* mine = wl + (int64_t)i * W;
+    const int32_t* mine_id = wid + (int64_t)i * W;
+    const int n = clampi(wc[i], 0, W);
+    int k = 0;
+    for (int p = 0; p < n; ++p) {
+        const int c = mine_id[p], j = mine[p];
+        if (c < 0 || c >= C || flag[c] != 0) continue;
+        int q = k;  // k <= p: entry p was read above, the entries behind it are untouched
+        for (; q > 0 && mine[q - 1] > j; --q) mine[q] = mine[q - 1];
+        mine[q] = j;
+        ++k;
+    }
+    wc[i] = k;
+}
+
 }  // namespace
 
 extern "C" {
@@ -255,6 +426,64 @@ int mgn_world_topology_build(const float* pos, int64_t ld_pos, const float* node
     hipLaunchKernelGGL(world_merge, dim3((unsigned)cdiv64(N * WORLD_MERGE_LANES, 256)), dim3(256), 0, st, mesh_ptr,
                        mesh_nbr, e_m, wl, wc, (int)W, n, e_cap, col_ptr, csc_src, csc_dst, csc_eid, row_perm,
                        edge_index, err_word);
+    MGN_LAUNCH_CHECK();
+    return 0;
+}
+
+size_t mgn_random_topology_workspace_bytes(int64_t num_nodes, int32_t max_new, int64_t num_candidates) {
+    const int64_t n = num_nodes < 1 ? 1 : num_nodes, w = max_new < 1 ? 1 : max_new;
+    const int64_t c = num_candidates < 1 ? 1 : num_candidates;
+    // wc, wl, the candidate id beside every entry of wl, the flags, the mapped endpoints, and the word world_merge
+    // flags a bad mesh in
+    return al((size_t)n * 4) + 2 * al((size_t)n * (size_t)w * 4) + al((size_t)c * 4) + al((size_t)c * 8) + al(4);
+}
+
+int mgn_random_topology_build(const int32_t* pairs, const int32_t* cand_ptr, int64_t C, const int32_t* graph_ptr,
+                              int32_t B, int64_t N, const int32_t* mesh_ptr, const int32_t* mesh_nbr, int64_t E_m,
+                              int32_t W, const int32_t* enabled, int32_t* csc_src, int32_t* csc_dst, int32_t* csc_eid,
+                              int32_t* col_ptr, int32_t* row_ptr, int32_t* row_perm, int64_t* edge_index,
+                              int32_t* num_edges, void* ws, size_t ws_bytes, mgn_stream_t stream) {
+    const std::string who = "random_topology_build";
+    MGN_REQUIRE(N >= 0 && B >= 0 && E_m >= 0 && C >= 0, who + ": N, B, E_m and num_candidates must be >= 0");
+    MGN_REQUIRE(W >= 1 && W <= RANDOM_MAX_NEW, who + ": max_new must lie in [1, 64]");
+    MGN_REQUIRE(N <= (1ll << 30) && E_m <= INT32_MAX && E_m + N * (int64_t)W <= INT32_MAX,
+                who + ": N must be <= 2^30 and E_m + N * max_new must fit int32");
+    MGN_REQUIRE(C <= (1ll << 30), who + ": num_candidates must be <= 2^30");
+    MGN_REQUIRE(enabled != nullptr, who + ": NULL enabled word");
+    MGN_REQUIRE(num_edges != nullptr && col_ptr != nullptr && row_ptr != nullptr, who + ": a null pointer argument");
+    MGN_REQUIRE(ws_bytes >= mgn_random_topology_workspace_bytes(N, W, C), who + ": workspace too small");
+    if (N == 0) return 0;
+    MGN_REQUIRE(B >= 1, who + ": nodes without a graph (B == 0)");
+    MGN_REQUIRE((pairs || C == 0) && cand_ptr && graph_ptr && mesh_ptr && (mesh_nbr || E_m == 0) && csc_src &&
+                    csc_dst && csc_eid && row_perm && edge_index && ws,
+                who + ": a null pointer argument");
+    hipStream_t st = (hipStream_t)stream;
+    char* w = reinterpret_cast<char*>(ws);
+    int32_t* wc = reinterpret_cast<int32_t*>(w); w += al((size_t)N * 4);
+    int32_t* wl = reinterpret_cast<int32_t*>(w); w += al((size_t)N * (size_t)W * 4);
+    int32_t* wid = reinterpret_cast<int32_t*>(w); w += al((size_t)N * (size_t)W * 4);
+    int32_t* flag = reinterpret_cast<int32_t*>(w); w += al((size_t)(C < 1 ? 1 : C) * 4);
+    int2* mapped = reinterpret_cast<int2*>(w); w += al((size_t)(C < 1 ? 1 : C) * 8);
+    uint32_t* sink = reinterpret_cast<uint32_t*>(w);  // world_merge's error word: the caller validated the mesh
+    const int n = (int)N, e_m = (int)E_m, e_cap = (int)(E_m + N * (int64_t)W);
+    const unsigned blocks = (unsigned)cdiv64(N, WORLD_THREADS);
+    if (C > 0) {
+        MGN_TRY(hipMemsetAsync(flag, 0, (size_t)C * 4, st));
+        hipLaunchKernelGGL(random_map, dim3((unsigned)cdiv64(C, WORLD_THREADS)), dim3(WORLD_THREADS), 0, st, pairs,
+                           cand_ptr, (int)C, graph_ptr, (int)B, n, enabled, mapped);
+        MGN_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(random_search, dim3(blocks), dim3(WORLD_THREADS), 0, st, mapped, cand_ptr, (int)C, graph_ptr,
+                       (int)B, n, mesh_ptr, mesh_nbr, e_m, (int)W, enabled, wl, wid, wc, flag);
+    MGN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(random_filter, dim3(blocks), dim3(WORLD_THREADS), 0, st, n, (int)W, (int)C, wl, wid, wc, flag);
+    MGN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(world_scan, dim3(1), dim3(WORLD_SCAN_THREADS), 0, st, mesh_ptr, e_m, wc, n, e_cap, col_ptr,
+                       row_ptr, num_edges);
+    MGN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(world_merge, dim3((unsigned)cdiv64(N * WORLD_MERGE_LANES, 256)), dim3(256), 0, st, mesh_ptr,
+                       mesh_nbr, e_m, wl, wc, (int)W, n, e_cap, col_ptr, csc_src, csc_dst, csc_eid, row_perm,
+                       edge_index, sink);
     MGN_LAUNCH_CHECK();
     return 0;
 }

@@ -202,6 +202,9 @@ EXPORTS = {
     "mgn_world_topology_workspace_bytes": (_sz, [_i64, _i32]),
     "mgn_world_topology_build": (_i32, [_vp, _i64, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _i64, _dbl, _i32, _vp, _vp,
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mgn_random_topology_workspace_bytes": (_sz, [_i64, _i32, _i64]),
+    "mgn_random_topology_build": (_i32, [_vp, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mgn_feed_inflow_capacity": (_i32, []),
     "mgn_feed_inflow_stats": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp]),
     "mgn_feed_batch_aneurysm": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, FeedRanges8,
@@ -728,6 +731,61 @@ def world_topology_build(pos, node_type, graph_ptr, mesh_ptr, mesh_nbr, radius, 
         ptr(csc_dst), ptr(csc_eid), ptr(col_ptr), ptr(row_ptr), ptr(row_perm), ptr(ei), ptr(num_edges), ew.ptr(),
         ptr(ws), ws.numel(), stream_ptr(dev)))
     ew.arm()
+
+
+RANDOM_MAX_NEW = 64  # mgn.h: the largest max_new of mgn_random_topology_build
+
+
+def random_topology_workspace(N, max_new, num_candidates, device):
+    """The scratch of one mgn_random_topology_build over N nodes and num_candidates pairs (uint8, caller-kept)."""
+    import torch
+
+    n = lib().mgn_random_topology_workspace_bytes(int(N), int(max_new), int(num_candidates))
+    return torch.empty(max(int(n), 1), dtype=torch.uint8, device=device)
+
+
+def random_topology_build(pairs, cand_ptr, graph_ptr, mesh_ptr, mesh_nbr, max_new, enabled, csc_src, csc_dst, csc_eid,
+                          col_ptr, row_ptr, row_perm, edge_index, num_edges, ws):
+    """The topology of mesh edges ∪ the surviving random pairs of `pairs` (mgn_random_topology_build; the rule:
+    dataset.resident.random_topology_torch): pairs int32 [C, 2] of non-negative draws, cand_ptr int32 [B + 1] the
+    candidate offsets of every graph (from 0 to C, non-decreasing: the caller built it on the host), graph_ptr int32
+    [B + 1], mesh_ptr int32 [N + 1] / mesh_nbr int32 [E_m] the static adjacency as CSR, enabled int32 [1] (0: the mesh
+    alone). Writes the six arrays ([E_cap] and [N + 1] int32, E_cap = E_m + N · max_new), edge_index int64 [2, E_cap]
+    and num_edges int32 [1] in place on the current stream. Nothing is read back and no error bit is set: a node over
+    capacity drops candidates."""
+    import torch
+
+    require_device(pairs)
+    dev, N, E_m, W = pairs.device, mesh_ptr.numel() - 1, mesh_nbr.numel(), int(max_new)
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous():
+        raise ValueError("random_topology_build: pairs must be a contiguous int32 [C, 2] tensor")
+    C = pairs.shape[0]
+    if not 1 <= W <= RANDOM_MAX_NEW:
+        raise ValueError(f"random_topology_build: max_new {W} must lie in [1, {RANDOM_MAX_NEW}]")
+    E_cap = E_m + N * W
+    B1 = graph_ptr.numel()
+    for name, a, n in (("graph_ptr", graph_ptr, None), ("cand_ptr", cand_ptr, B1), ("mesh_ptr", mesh_ptr, N + 1),
+                       ("mesh_nbr", mesh_nbr, E_m), ("enabled", enabled, 1),
+                       ("csc_src", csc_src, max(E_cap, 1)), ("csc_dst", csc_dst, max(E_cap, 1)),
+                       ("csc_eid", csc_eid, max(E_cap, 1)), ("row_perm", row_perm, max(E_cap, 1)),
+                       ("col_ptr", col_ptr, N + 1), ("row_ptr", row_ptr, N + 1), ("num_edges", num_edges, 1)):
+        if a.dtype != torch.int32 or a.dim() != 1 or not a.is_contiguous() or a.device != dev or \
+                (n is not None and a.numel() != n):
+            raise ValueError(f"random_topology_build: {name} must be a contiguous int32 "
+                             f"[{'B + 1' if n is None else n}] tensor on pairs' device")
+    if B1 < 1 or (N > 0 and B1 < 2):
+        raise ValueError("random_topology_build: graph_ptr must hold B + 1 node offsets")
+    ei = edge_index
+    if ei.dtype != torch.int64 or tuple(ei.shape) != (2, max(E_cap, 1)) or not ei.is_contiguous() or ei.device != dev:
+        raise ValueError(f"random_topology_build: edge_index must be a contiguous int64 [2, {max(E_cap, 1)}] tensor on "
+                         "pairs' device")
+    wsb = int(lib().mgn_random_topology_workspace_bytes(N, W, C))
+    if ws.dtype != torch.uint8 or ws.numel() < wsb or ws.device != dev:
+        raise ValueError(f"random_topology_build: ws must hold {wsb} bytes on pairs' device")
+    check(lib().mgn_random_topology_build(
+        ptr(pairs), ptr(cand_ptr), C, ptr(graph_ptr), B1 - 1, N, ptr(mesh_ptr), ptr(mesh_nbr), E_m, W, ptr(enabled),
+        ptr(csc_src), ptr(csc_dst), ptr(csc_eid), ptr(col_ptr), ptr(row_ptr), ptr(row_perm), ptr(ei), ptr(num_edges),
+        ptr(ws), ws.numel(), stream_ptr(dev)))
 
 
 def feed_ranges8(ranges):

@@ -45,12 +45,36 @@ the six arrays of the feed's topology, its edge_index and its edge count. batch.
 bound to that topology (models._engine.bind_topology), so a recorded step keeps reading the same addresses and every
 replay attends over the contacts of its own batch. world_topology_torch states the rule.
 
-Not supported: `previous_data` outside aneurysm= (there it is the frame before the drawn one), dynamic_edges= for
-models with edge_attr (the MGN path: its launch shapes depend on the edge count; the edge_index given inside
-world_pos= stays static for the life of the feed), rotate= together with world_pos=, aneurysm= together with either,
-a wall flag that changes over time (aneurysm= takes the node types from frame 0), and trajectories of unequal length
-in one batch. batch.edge_index is written only by a dynamic_edges= feed (through its own tensor), batch.edge_attr
-only by a rotating feed that was given a clean edge_attr and by a world_pos= feed that was given an edge_index.
+Random long-range edges (random_edges=; the reference's BaseDataset._add_random_edges, dataset/dataset.py:104-137,
+the dataset.new_edges_ratio of every transformer config: per item PyG's add_random_edge(p, force_undirected=True) adds
+"random jumps", a new set of long-range attention partners on every sample): after the fill, the feed draws its
+candidate pairs (pairs.random_(0, 2**31 − 1): torch's generator, recorded, new on every replay) and
+mgn_random_topology_build rewrites the feed's topology, edge_index and edge count in place, as dynamic_edges= does.
+random_topology_torch states the rule:
+  * graph g with n_g nodes and E_g directed mesh edges has the fixed number C_g = round(ratio · E_g) // 2 of candidate
+    pairs (add_random_edge asks for round(p · E) directed edges and samples half as many unordered pairs), none when
+    n_g < 2; candidate c of graph g is (u, v) = pairs[c], with the endpoints a = lo_g + u % n_g, b = lo_g + v % n_g;
+  * for node i, over its graph's candidates in order, a candidate is live when i is an endpoint, a != b, and the
+    other endpoint j is no mesh neighbour of i. Pass 1 keeps a list L_i: a live candidate whose j is in L_i is skipped
+    (a repeat); else, when L_i holds max_new entries, the candidate is dropped (flagged); else j is appended, c beside
+    it. Pass 2: i's new neighbours are the entries of L_i whose candidate is unflagged, ascending;
+  * an unordered pair survives exactly when its first candidate is unflagged, at both endpoints alike, so the lists
+    are symmetric; the result is the union of the mesh edges and the lists, sorted by (row, col), every edge once.
+Dropping is the capacity policy here, where dynamic_edges= raises: there an edge over capacity is physics lost; here the
+number of new neighbours of a node is about Poisson with mean ratio · degree, some node of a large batch overflows
+once in a few thousand steps, and a training run must not stop for that. Relation to PyG — recalled, not checked: PyG
+is not installed here and the reference holds none of its code — add_random_edge routes through negative_sampling,
+which samples non-edges without replacement; this rule samples with replacement and discards self-pairs, mesh edges and
+repeats without redrawing, so it adds slightly fewer edges, by a fraction of about (1 + degree) / n_g + C_g / (n_g² / 2).
+The distribution follows PyG's; the draws for a seed do not.
+
+Not supported: `previous_data` outside aneurysm= (there it is the frame before the drawn one), dynamic_edges= and
+random_edges= for models with edge_attr (the MGN path: its launch shapes depend on the edge count; the edge_index given
+inside world_pos= stays static for the life of the feed), the two together, rotate= together with world_pos=, aneurysm=
+together with either, a wall flag that changes over time (aneurysm= takes the node types from frame 0), and trajectories
+of unequal length in one batch. batch.edge_index is written only by a dynamic_edges= or random_edges= feed (through its
+own tensor), batch.edge_attr only by a rotating feed that was given a clean edge_attr and by a world_pos= feed that was
+given an edge_index.
 
 The validation rollout reads the same resident frames (training.rollout.Rollout.rollout_resident):
 rollout_begin_torch / rollout_end_torch state, as torch ops on any device, the two rules libmgn's
@@ -357,7 +381,13 @@ def world_topology_torch(pos, node_type, graph_ptr, mesh_edge_index, radius, max
     if max_neighbors is not None and world_key.numel() and \
             int(torch.bincount(torch.div(world_key, max(N, 1), rounding_mode="floor")).max()) > int(max_neighbors):
         raise nat.world_capacity_error()
-    key = torch.sort(torch.cat([mesh_key, world_key])).values
+    return _topology_of_keys(torch.sort(torch.cat([mesh_key, world_key])).values, N)
+
+
+def _topology_of_keys(key, N):
+    """(edge_index, arrays) of a symmetric adjacency given as its ascending, unique keys row · N + col: what
+    world_topology_torch and random_topology_torch return."""
+    dev = key.device
     row, col = torch.div(key, max(N, 1), rounding_mode="floor"), key % max(N, 1)
     ptr = torch.searchsorted(row.contiguous(), torch.arange(N + 1, device=dev)).to(torch.int32)
     # target-sorted position k holds edge (src = col[k] → dst = row[k]); its id in (row, col) order is the rank of
@@ -368,6 +398,87 @@ def world_topology_torch(pos, node_type, graph_ptr, mesh_edge_index, radius, max
     arrays = {"csc_src": col.to(torch.int32), "csc_dst": row.to(torch.int32), "csc_eid": eid.to(torch.int32),
               "row_perm": perm.to(torch.int32), "col_ptr": ptr, "row_ptr": ptr.clone()}
     return torch.stack([row, col]), arrays
+
+
+def random_candidate_ptr(graph_ptr, mesh_edge_index, ratio):
+    """The candidate offsets [B + 1] (a host list) of a random_edges= feed: graph g with n_g nodes and E_g directed
+    mesh edges gets C_g = round(ratio · E_g) // 2 candidate pairs — PyG's add_random_edge(p, force_undirected=True)
+    asks for round(p · E) directed edges and samples half as many unordered pairs — and none when n_g < 2."""
+    gp = [int(v) for v in (graph_ptr.tolist() if torch.is_tensor(graph_ptr) else graph_ptr)]
+    row = mesh_edge_index[0].to("cpu", torch.int64).contiguous()
+    bounds = torch.searchsorted(row, torch.tensor(gp, dtype=torch.int64)).tolist()  # the mesh is sorted by row
+    ptr = [0]
+    for g in range(len(gp) - 1):
+        E_g = bounds[g + 1] - bounds[g]
+        ptr.append(ptr[-1] + (round(float(ratio) * E_g) // 2 if gp[g + 1] - gp[g] >= 2 else 0))
+    return ptr
+
+
+def random_topology_torch(pairs, graph_ptr, mesh_edge_index, max_new, enabled=True, *, cand_ptr):
+    """mgn_random_topology_build's rule as torch ops on any device (module docstring, "Random long-range edges").
+    pairs: integer [C, 2], non-negative; cand_ptr: [B + 1] candidate offsets of every graph, from 0 to C
+    (random_candidate_ptr); mesh_edge_index: check_mesh_edges' preconditions. Candidate c of graph g = [lo_g, lo_g +
+    n_g) has the endpoints a = lo_g + pairs[c, 0] % n_g and b = lo_g + pairs[c, 1] % n_g. For node i, over its graph's
+    candidates in order, a candidate is live when i is an endpoint, a != b and the other endpoint j is no mesh
+    neighbour of i; pass 1 keeps a list L_i: a live candidate whose j is in L_i is skipped, else with |L_i| == max_new
+    it is dropped (flagged), else j is appended with c beside it; pass 2: i's new neighbours are the entries of L_i
+    whose candidate is unflagged, ascending. The result is the union of the mesh edges and those lists (they are
+    symmetric), sorted by (row, col), every edge once: returns (edge_index int64 [2, E], arrays) as
+    world_topology_torch does. enabled False: the mesh alone. No error for a node over max_new: dropping is the
+    capacity policy.
+
+    Vectorised, not walked: a candidate gives two events (i, j, c) = (a, b, c), (b, a, c). Of the live events with the
+    same (i, j) only the first in candidate order can append — a later one finds j in L_i, or, when the first was
+    dropped, finds the list still full (lists only grow in pass 1) and is dropped as well, being in no list; the k-th
+    such first event of node i, in candidate order, is appended when k < max_new and flags its candidate otherwise.
+    What a random_edges= feed runs on CPU tensors, and what the kernels are tested against."""
+    gp = [int(v) for v in (graph_ptr.tolist() if torch.is_tensor(graph_ptr) else graph_ptr)]
+    cp = [int(v) for v in (cand_ptr.tolist() if torch.is_tensor(cand_ptr) else cand_ptr)]
+    N, W, dev = gp[-1], int(max_new), pairs.device
+    C = pairs.shape[0]
+    if len(cp) != len(gp) or cp[0] != 0 or cp[-1] != C or any(b < a for a, b in zip(cp, cp[1:])):
+        raise ValueError(f"cand_ptr must hold B + 1 = {len(gp)} non-decreasing candidate offsets from 0 to C = {C}, "
+                         f"got {cp}")
+    if W < 1:
+        raise ValueError(f"max_new {max_new} must be >= 1")
+    mesh = mesh_edge_index.to(dev, torch.int64)
+    mesh_key = mesh[0] * N + mesh[1]
+    if not enabled or C == 0:
+        return _topology_of_keys(mesh_key, N)
+    counts = torch.tensor([b - a for a, b in zip(cp, cp[1:])], dtype=torch.int64, device=dev)
+    graph = torch.repeat_interleave(torch.arange(len(cp) - 1, device=dev), counts, output_size=C)
+    lo = torch.tensor(gp[:-1], dtype=torch.int64, device=dev)[graph]
+    n = torch.tensor([b - a for a, b in zip(gp, gp[1:])], dtype=torch.int64, device=dev)[graph]
+    if bool((n < 1).any()):
+        raise ValueError("cand_ptr gives candidates to a graph without nodes")
+    p = pairs.to(torch.int64)
+    if bool((p < 0).any()):
+        raise ValueError("pairs must be non-negative")
+    a, b = lo + p[:, 0] % n, lo + p[:, 1] % n
+    # events in candidate order: 2c is (a, b, c), 2c + 1 is (b, a, c)
+    ev_i, ev_j = torch.stack([a, b], dim=1).reshape(-1), torch.stack([b, a], dim=1).reshape(-1)
+    ev_c = torch.arange(C, device=dev).repeat_interleave(2)
+    key = ev_i * N + ev_j
+    live = (ev_i != ev_j) & ~torch.isin(key, mesh_key)
+    key, ev_c = key[live], ev_c[live]
+    # the first event of every (i, j): a stable sort by key keeps candidate order inside a run
+    order = torch.sort(key, stable=True).indices
+    key, ev_c = key[order], ev_c[order]
+    first = torch.ones_like(key, dtype=torch.bool)
+    first[1:] = key[1:] != key[:-1]
+    key, ev_c = key[first], ev_c[first]
+    # its place among node i's first events, in candidate order
+    order = torch.sort(ev_c, stable=True).indices
+    key, ev_c = key[order], ev_c[order]
+    ev_i = torch.div(key, max(N, 1), rounding_mode="floor")
+    order = torch.sort(ev_i, stable=True).indices
+    key, ev_c, ev_i = key[order], ev_c[order], ev_i[order]
+    start = torch.searchsorted(ev_i.contiguous(), ev_i.contiguous())  # the first event of the node's run
+    appended = torch.arange(key.numel(), device=dev) - start < W
+    flag = torch.zeros(C, dtype=torch.bool, device=dev)
+    flag[ev_c[~appended]] = True
+    new_key = key[appended & ~flag[ev_c]]
+    return _topology_of_keys(torch.sort(torch.cat([mesh_key, new_key])).values, N)
 
 
 def check_rollout_columns(F, y_columns, out_columns, prev_columns, node_type_index):
@@ -576,15 +687,30 @@ class ResidentTrajectories:
     the statistics of every frame that has a successor; refresh_stats() recomputes that table. Frames are drawn
     over [1, T − 2] (frame t − 1 is read) and set_frames refuses 0. A graph whose inflow nodes make more than
     MGN_FEED_INFLOW_CAPACITY values is refused. Not together with rotate= or world_pos=. Its validation rollout:
-    Rollout(..., feed=, acceleration="frame" | "prediction")."""
+    Rollout(..., feed=, acceleration="frame" | "prediction").
+
+    random_edges: None, or new random long-range edges on every fill for a model without edge_attr (module docstring),
+    as a dict
+      {"edge_index": mesh_ei,    # [2, E_m]: the batch's mesh edges, check_mesh_edges' preconditions as for dynamic_edges
+       "ratio": 0.5,             # the reference's dataset.new_edges_ratio, in (0, 1]
+       "max_new": 16}            # capacity: the most new neighbours one node may get, in [1, 64]; more are dropped
+    The feed then owns topology (models._engine.RandomTopology; None on CPU tensors), edge_index (int64 [2, E_cap],
+    E_cap = E_m + N · max_new: the tensor the caller puts into batch.edge_index), num_edges_dev (int32 [1]), pairs
+    (int32 [C, 2], the candidates of the last fill), cand_ptr (int32 [B + 1]) and random_enabled (int32 [1]). fill
+    draws pairs and calls build_random_edges(). set_random_edges(False) makes every build write the mesh adjacency
+    (validation) without a new recording; set_pairs gives explicit pairs (tests). With the plain fill, with aneurysm=
+    and with a world_pos= that has no edge side; not with dynamic_edges=, a rotate= that carries an edge_attr, or a
+    world_pos= with an edge_index. Rollout.rollout_resident on such a feed does not rebuild: it runs on the topology of
+    the last build_random_edges(); for validation, feed.set_random_edges(False); feed.build_random_edges()."""
 
     ROTATE_KEYS = ("feature_indices", "edge_attr", "edge_index", "edge_feature_indices")
     WORLD_KEYS = ("world_pos_index_start", "world_pos_index_end", "node_type_index", "edge_index", "edge_attr_start")
     ANEURYSM_KEYS = ("pos",)
     DYNAMIC_KEYS = ("edge_index", "radius", "max_neighbors")
+    RANDOM_KEYS = ("edge_index", "ratio", "max_new")
 
     def __init__(self, traj, graph_ptr, y_columns, node_type_index, noise=None, frames="random", rotate=None,
-                 world_pos=None, aneurysm=None, dynamic_edges=None):
+                 world_pos=None, aneurysm=None, dynamic_edges=None, random_edges=None):
         if not torch.is_tensor(traj) or traj.dtype != torch.float32 or traj.dim() != 3 or not traj.is_contiguous():
             raise ValueError("traj must be a contiguous fp32 [T, N, F] tensor")
         T, N, F = traj.shape
@@ -612,6 +738,16 @@ class ResidentTrajectories:
                 raise ValueError("dynamic_edges= together with rotate= or aneurysm= is not supported")
             if world_pos is None:
                 raise ValueError("dynamic_edges= needs world_pos=: the world edges follow the world positions")
+        if random_edges is not None:
+            if dynamic_edges is not None:
+                raise ValueError("random_edges= together with dynamic_edges= is not supported: one topology per feed")
+            if isinstance(rotate, dict) and rotate.get("edge_attr") is not None:
+                raise ValueError("random_edges= together with a rotate= that carries an edge_attr is not supported: "
+                                 "models with edge_attr are not supported (their launch shapes depend on the edge "
+                                 "count)")
+            if isinstance(world_pos, dict) and world_pos.get("edge_index") is not None:
+                raise ValueError("random_edges= needs a world_pos= without edge_index / edge_attr_start: models with "
+                                 "edge_attr are not supported (their launch shapes depend on the edge count)")
         self.traj, self.T, self.N, self.F, self.B = traj, T, N, F, len(gp) - 1
         self.y_columns, self.node_type_index = (ys, ye), int(node_type_index)
         dev = traj.device
@@ -629,6 +765,12 @@ class ResidentTrajectories:
         self.topology, self.edge_index, self.num_edges_dev, self.topology_arrays = None, None, None, None
         if self.dynamic:
             self._init_dynamic(dynamic_edges, gp)
+        # random_edges=: new long-range edges on every fill, as a topology rebuilt in place (see build_random_edges)
+        self.random = random_edges is not None
+        self.pairs, self.cand_ptr, self.random_enabled = None, None, None
+        self.random_pairs = None  # None: no random edges; True: drawn on every fill; False: explicit pairs
+        if self.random:
+            self._init_random(random_edges, gp)
         self.pos, self.node_type, self.inflow_stats, self.inflow_ptr, self.inflow_rows = None, None, None, None, None
         if self.aneurysm:
             self._init_aneurysm(aneurysm, gp)
@@ -750,9 +892,88 @@ class ResidentTrajectories:
 
     def current_edge_index(self):
         """edge_index[:, :num_edges] of the last build, a view (reads the count back: for CPU models and tests)."""
-        if not self.dynamic:
+        if not self.dynamic and not self.random:
             raise ValueError("current_edge_index: this feed was built without dynamic_edges=")
         return self.edge_index[:, :int(self.num_edges_dev)]
+
+    def _init_random(self, re, gp):
+        if not isinstance(re, dict) or any(k not in self.RANDOM_KEYS for k in re) or \
+                any(k not in re for k in self.RANDOM_KEYS):
+            raise ValueError(f"random_edges must be a dict with the keys {self.RANDOM_KEYS}, got {re!r}")
+        ratio, W = re["ratio"], re["max_new"]
+        if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not 0.0 < float(ratio) <= 1.0:
+            raise ValueError(f"random_edges ratio {ratio!r} must lie in (0, 1] (the reference's new_edges_ratio)")
+        if isinstance(W, bool) or not isinstance(W, int) or not 1 <= W <= nat.RANDOM_MAX_NEW:
+            raise ValueError(f"random_edges max_new {W!r} must be an int in [1, {nat.RANDOM_MAX_NEW}]")
+        dev, N = self.traj.device, self.N
+        mesh = check_mesh_edges(re["edge_index"], gp, N)
+        E_cap = mesh.shape[1] + N * W
+        if E_cap > 2 ** 31 - 1:
+            raise ValueError(f"random_edges: E_m + N * max_new = {E_cap} does not fit int32")
+        self.ratio, self.max_new, self._gp_list = float(ratio), W, gp
+        self._cand_list = random_candidate_ptr(gp, mesh, self.ratio)
+        self.mesh_edge_index = mesh.to(dev)
+        self.cand_ptr = torch.tensor(self._cand_list, dtype=torch.int32, device=dev)
+        self.pairs = torch.zeros(self._cand_list[-1], 2, dtype=torch.int32, device=dev)
+        self.random_enabled = torch.ones(1, dtype=torch.int32, device=dev)
+        self.random_pairs = True
+        if dev.type == "cuda":
+            from graphphysics.models import _engine
+
+            self.topology = _engine.RandomTopology(mesh, gp, N, self._cand_list, W, dev)
+            self.edge_index, self.num_edges_dev = self.topology.edge_index, self.topology.num_edges_dev
+            _engine.bind_topology(self.edge_index, self.topology)
+        else:
+            self.edge_index = torch.zeros(2, max(E_cap, 1), dtype=torch.int64)
+            self.num_edges_dev = torch.zeros(1, dtype=torch.int32)
+
+    def build_random_edges(self):
+        """Rebuild the topology from the feed's pairs and its random_enabled word: HIP tensors,
+        mgn_random_topology_build into self.topology (device work only, capturable); CPU tensors,
+        random_topology_torch into edge_index[:, :E], num_edges_dev and topology_arrays. fill calls it after its draw;
+        for validation, feed.set_random_edges(False); feed.build_random_edges() leaves the mesh adjacency."""
+        if not self.random:
+            raise ValueError("build_random_edges: this feed was built without random_edges=")
+        if self.pairs.is_cuda:
+            self.topology.build(self.pairs, self.random_enabled)
+            return
+        ei, arrays = random_topology_torch(self.pairs, self._gp_list, self.mesh_edge_index, self.max_new,
+                                           bool(int(self.random_enabled)), cand_ptr=self._cand_list)
+        self.edge_index[:, :ei.shape[1]] = ei
+        self.num_edges_dev.fill_(ei.shape[1])
+        self.topology_arrays = arrays
+
+    def set_random_edges(self, enabled):
+        """Switch the random edges off (every build then writes the mesh adjacency: validation) or on again. Rewrites
+        the persistent random_enabled word, which a captured graph reads at replay: no re-capture."""
+        if not self.random:
+            raise ValueError("set_random_edges: this feed was built without random_edges=")
+        self.random_enabled.fill_(1 if enabled else 0)
+
+    def set_pairs(self, pairs):
+        """"random" (the default of a feed with random_edges=): every fill draws pairs.random_(0, 2**31 - 1). An integer
+        [C, 2] host list / CPU tensor of non-negative values below 2**31: the fills use these until the next
+        set_pairs (for tests). ValueError without random_edges=, or for another shape."""
+        if not self.random:
+            raise ValueError("set_pairs: this feed was built without random_edges=")
+        C = self.pairs.shape[0]
+        if isinstance(pairs, str):
+            if pairs != "random":
+                raise ValueError(f'pairs must be "random" or an integer [{C}, 2] tensor, got {pairs!r}')
+            self.random_pairs = True
+            return
+        p = torch.as_tensor(pairs).cpu()
+        if p.is_floating_point() or p.dtype == torch.bool or tuple(p.shape) != (C, 2):
+            raise ValueError(f"expected integer pairs [{C}, 2], got {tuple(p.shape)} {p.dtype}")
+        if C and (int(p.min()) < 0 or int(p.max()) > 2 ** 31 - 1):
+            raise ValueError("pairs must lie in [0, 2**31 - 1]")
+        self.random_pairs = False
+        self.pairs.copy_(p.to(torch.int32))
+
+    def _fill_random(self):
+        if self.random_pairs:
+            self.pairs.random_(0, 2 ** 31 - 1)  # torch's generator: recorded, and new on every replay
+        self.build_random_edges()
 
     def _init_aneurysm(self, an, gp):
         if not isinstance(an, dict) or any(k not in self.ANEURYSM_KEYS for k in an) or "pos" not in an:
@@ -906,7 +1127,10 @@ class ResidentTrajectories:
         world_edge_features_torch. With aneurysm=: batch.x[:, :F + 10], one mgn_feed_batch_aneurysm in
         mgn_feed_batch's place (the statistics table was built at construction); CPU tensors: fill_aneurysm_torch.
         With dynamic_edges=: after the world fill, build_edges on the noisy x (mgn_world_topology_build, three
-        launches; CPU tensors: world_topology_torch), and batch.edge_index must be the feed's edge_index."""
+        launches; CPU tensors: world_topology_torch), and batch.edge_index must be the feed's edge_index. With
+        random_edges=: after any of these fills, the draw of pairs and build_random_edges (mgn_random_topology_build,
+        a memset and five launches; CPU tensors: random_topology_torch), and batch.edge_index must be the feed's
+        edge_index."""
         x, y = batch.x, batch.y
         if x.device != self.traj.device or x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != self.N or \
                 x.shape[1] < self.Fx:
@@ -935,6 +1159,9 @@ class ResidentTrajectories:
         if self.dynamic and x.is_cuda and getattr(batch, "edge_index", None) is not self.edge_index:
             raise ValueError("with dynamic_edges=, batch.edge_index must be the feed's own edge_index tensor "
                              "(feed.edge_index): it is the handle of the topology the fill rebuilds")
+        if self.random and x.is_cuda and getattr(batch, "edge_index", None) is not self.edge_index:
+            raise ValueError("with random_edges=, batch.edge_index must be the feed's own edge_index tensor "
+                             "(feed.edge_index): it is the handle of the topology the fill rebuilds")
         with torch.no_grad():
             if self.random_frames:
                 # torch.randint(0, T-1, (B,)) into the persistent tensor; aneurysm=: frame t - 1 is read too
@@ -951,6 +1178,8 @@ class ResidentTrajectories:
                                                  self.inflow_stats, self.y_columns, self.ranges, self.scales, self.z)
                     x[:, :self.Fx] = fx
                     y.copy_(fy)
+                if self.random:
+                    self._fill_random()
                 return batch
             if self.world:
                 if self.traj.is_cuda:
@@ -968,6 +1197,8 @@ class ResidentTrajectories:
                         world_edge_features_torch(x, self._world_edge_index, wea, self.edge_attr_start)
                 if self.dynamic:  # add_world_edges reads the (noisy) world positions and the batch's node types
                     self.build_edges(x, x[:, self.node_type_index + 3])
+                if self.random:
+                    self._fill_random()
                 return batch
             if rot and self.random_rotations:
                 self.angles.uniform_(-math.pi, math.pi)  # one rotation per graph, as the reference's per item
@@ -995,4 +1226,6 @@ class ResidentTrajectories:
                 if ea is not None:
                     ea[:, :self.edge_attr.shape[1]] = rotate_rows_torch(self.edge_attr, self.row_graph,
                                                                         self.edge_triples, self.R)
+            if self.random:
+                self._fill_random()
         return batch

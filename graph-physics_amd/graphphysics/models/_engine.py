@@ -5,6 +5,8 @@
 * DynamicTopology — the same arrays at a fixed capacity, rebuilt in place on the device from the step's positions
                    (mesh edges ∪ per-frame world edges, mgn_world_topology_build); bind_topology ties it to the
                    edge_index tensor that stands for it.
+* RandomTopology — the same, rebuilt from a tensor of random bits (mesh edges ∪ random long-range pairs,
+                   mgn_random_topology_build).
 * MlpSpec        — one build_mlp nn.Sequential (reference graphphysics/models/layers.py:77-113)
                    seen by the kernels: its Linear weights are packed into MFMA fragments, biases and
                    RMSNorm scale are read straight from the fp32 master parameters.
@@ -63,7 +65,37 @@ class GraphTopology:
                                    self.row_ptr.data_ptr(), self.row_perm.data_ptr())
 
 
-class DynamicTopology:
+class _RebuiltTopology:
+    """What DynamicTopology and RandomTopology share: the static mesh adjacency as CSR, and the six arrays, edge_index
+    and the live edge count of a topology of the fixed capacity E_cap = E_m + N · per_node that a build rewrites in
+    place through raw pointers."""
+
+    def _init_arrays(self, mesh_edge_index, graph_ptr, num_nodes, per_node, device):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("the MI355X MGN path needs tensors on a HIP device (no CPU fallback)")
+        N, W = int(num_nodes), int(per_node)
+        ei = mesh_edge_index.to(torch.int64).cpu()
+        E_m = int(ei.shape[1])
+        E = E_m + N * W
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.num_nodes, self.num_edges, self.device = N, E, dev
+        self.num_mesh_edges = E_m
+        self.mesh_ptr = torch.searchsorted(ei[0].contiguous(), torch.arange(N + 1)).to(**i32)
+        self.mesh_nbr = ei[1].to(**i32).contiguous()
+        self.graph_ptr = torch.as_tensor(graph_ptr).to(**i32).contiguous()
+        # zeros: an entry a build over capacity leaves unwritten is still a valid index (mgn.h, "Capacity")
+        self.csc_src, self.csc_dst = torch.zeros(max(E, 1), **i32), torch.zeros(max(E, 1), **i32)
+        self.csc_eid, self.row_perm = torch.zeros(max(E, 1), **i32), torch.zeros(max(E, 1), **i32)
+        self.col_ptr, self.row_ptr = torch.zeros(N + 1, **i32), torch.zeros(N + 1, **i32)
+        self.edge_index = torch.zeros(2, max(E, 1), dtype=torch.int64, device=dev)
+        self.num_edges_dev = torch.zeros(1, **i32)
+        self.struct = nat.Topology(N, E, self.csc_src.data_ptr(), self.csc_dst.data_ptr(),
+                                   self.csc_eid.data_ptr(), self.col_ptr.data_ptr(),
+                                   self.row_ptr.data_ptr(), self.row_perm.data_ptr())
+
+
+class DynamicTopology(_RebuiltTopology):
     """A topology whose world edges are rebuilt on the device, inside a recorded step (mgn_world_topology_build,
     mgn.h "World edges inside the step"): the static mesh adjacency plus the OBSTACLE–NORMAL pairs of every graph
     that lie within `radius`, found anew from the positions of every build. Same attributes and `struct` as
@@ -77,30 +109,10 @@ class DynamicTopology:
     caller validates it: dataset.resident.check_mesh_edges); graph_ptr: [B + 1] node offsets."""
 
     def __init__(self, mesh_edge_index, graph_ptr, num_nodes, radius, max_neighbors, device):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("the MI355X MGN path needs tensors on a HIP device (no CPU fallback)")
-        N, W = int(num_nodes), int(max_neighbors)
-        ei = mesh_edge_index.to(torch.int64).cpu()
-        E_m = int(ei.shape[1])
-        E = E_m + N * W
-        i32 = dict(dtype=torch.int32, device=dev)
-        self.num_nodes, self.num_edges, self.device = N, E, dev
-        self.num_mesh_edges, self.radius, self.max_neighbors = E_m, float(radius), W
-        self.mesh_ptr = torch.searchsorted(ei[0].contiguous(), torch.arange(N + 1)).to(**i32)
-        self.mesh_nbr = ei[1].to(**i32).contiguous()
-        self.graph_ptr = torch.as_tensor(graph_ptr).to(**i32).contiguous()
-        # zeros: an entry a build over capacity leaves unwritten is still a valid index (mgn.h, "Capacity")
-        self.csc_src, self.csc_dst = torch.zeros(max(E, 1), **i32), torch.zeros(max(E, 1), **i32)
-        self.csc_eid, self.row_perm = torch.zeros(max(E, 1), **i32), torch.zeros(max(E, 1), **i32)
-        self.col_ptr, self.row_ptr = torch.zeros(N + 1, **i32), torch.zeros(N + 1, **i32)
-        self.edge_index = torch.zeros(2, max(E, 1), dtype=torch.int64, device=dev)
-        self.num_edges_dev = torch.zeros(1, **i32)
-        self._ws = nat.world_topology_workspace(N, W, dev)
-        nat.error_word(dev)  # exists before any capture
-        self.struct = nat.Topology(N, E, self.csc_src.data_ptr(), self.csc_dst.data_ptr(),
-                                   self.csc_eid.data_ptr(), self.col_ptr.data_ptr(),
-                                   self.row_ptr.data_ptr(), self.row_perm.data_ptr())
+        self._init_arrays(mesh_edge_index, graph_ptr, num_nodes, max_neighbors, device)
+        self.radius, self.max_neighbors = float(radius), int(max_neighbors)
+        self._ws = nat.world_topology_workspace(self.num_nodes, self.max_neighbors, self.device)
+        nat.error_word(self.device)  # exists before any capture
 
     def build(self, pos, node_type):
         """Rebuild from pos fp32 [N, >= 3] (unit column stride; e.g. the batch's x) and node_type fp32 [N] (any
@@ -108,6 +120,38 @@ class DynamicTopology:
         nat.world_topology_build(pos, node_type, self.graph_ptr, self.mesh_ptr, self.mesh_nbr, self.radius,
                                  self.max_neighbors, self.csc_src, self.csc_dst, self.csc_eid, self.col_ptr,
                                  self.row_ptr, self.row_perm, self.edge_index, self.num_edges_dev, self._ws)
+
+
+class RandomTopology(_RebuiltTopology):
+    """A topology whose random long-range edges are redrawn on the device, inside a recorded step
+    (mgn_random_topology_build, mgn.h "Random edges inside the step"): the static mesh adjacency plus the surviving
+    pairs of a tensor of random bits, by the rule of dataset.resident.random_topology_torch. Same attributes and
+    `struct` as DynamicTopology, over arrays of the fixed capacity E_cap = E_m + N · max_new; build() writes through raw
+    pointers, so bind_topology(self.edge_index, self) keeps get_topology and every recorded graph on this object.
+
+    mesh_edge_index, graph_ptr: as for DynamicTopology; cand_ptr: [B + 1] candidate offsets of every graph, non-
+    decreasing from 0 (dataset.resident.random_candidate_ptr)."""
+
+    def __init__(self, mesh_edge_index, graph_ptr, num_nodes, cand_ptr, max_new, device):
+        cp = [int(v) for v in (cand_ptr.tolist() if torch.is_tensor(cand_ptr) else cand_ptr)]
+        if len(cp) != len(graph_ptr) or not cp or cp[0] != 0 or any(b < a for a, b in zip(cp, cp[1:])):
+            raise ValueError(f"cand_ptr must hold B + 1 = {len(graph_ptr)} non-decreasing candidate offsets from 0, "
+                             f"got {cp}")
+        if not 1 <= int(max_new) <= nat.RANDOM_MAX_NEW:
+            raise ValueError(f"max_new {max_new} must lie in [1, {nat.RANDOM_MAX_NEW}]")
+        self._init_arrays(mesh_edge_index, graph_ptr, num_nodes, max_new, device)
+        self.max_new, self.num_candidates = int(max_new), cp[-1]
+        self.cand_ptr = torch.tensor(cp, dtype=torch.int32, device=self.device)
+        self._ws = nat.random_topology_workspace(self.num_nodes, self.max_new, self.num_candidates, self.device)
+
+    def build(self, pairs, enabled_dev):
+        """Rebuild from pairs int32 [C, 2] (non-negative draws) and enabled_dev int32 [1] (0: the mesh alone): one
+        memset and five launches on the current stream, capturable, nothing read back."""
+        if pairs.shape[0] != self.num_candidates:
+            raise ValueError(f"pairs must be int32 [{self.num_candidates}, 2], got {tuple(pairs.shape)}")
+        nat.random_topology_build(pairs, self.cand_ptr, self.graph_ptr, self.mesh_ptr, self.mesh_nbr, self.max_new,
+                                  enabled_dev, self.csc_src, self.csc_dst, self.csc_eid, self.col_ptr, self.row_ptr,
+                                  self.row_perm, self.edge_index, self.num_edges_dev, self._ws)
 
 
 # the block backward's weight-gradient halves run on a side stream, overlapped with the next block's

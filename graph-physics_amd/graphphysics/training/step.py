@@ -43,6 +43,9 @@ on a new batch and the host still only writes {lr, step}. Switching the feed bet
 frames re-records the step (the draw is, or is not, part of the graph). A feed built with rotate= also draws
 three angles per graph, builds the rotation matrices and rotates x, y and — into the step's private copy —
 edge_attr inside the same fill; switching set_rotations between drawn and explicit angles re-records as well.
+A feed built with random_edges= also draws its candidate pairs and rebuilds the topology behind batch.edge_index
+(which must be feed.edge_index) inside the fill, so every replay attends over new long-range edges; it is refused
+for a model that reads edge_attr, and switching set_pairs between drawn and explicit pairs re-records.
 
 Validation errors flagged on libmgn's device error word (out-of-range edge_index, node types outside
 the one-hot range) surface as the reference's IndexError / RuntimeError at most one step late,
@@ -91,7 +94,19 @@ class TrainStep:
         # feed (dataset.resident.ResidentTrajectories): its fill(batch) is the first device work of every
         # step — recorded at the head of the captured step, so each replay trains on newly drawn frames and noise
         self.feed = feed
-        self._feed_random = None  # the feed's (frame, rotation) draw modes the graph was recorded in
+        self._feed_random = None  # the feed's (frame, rotation, pair) draw modes the graph was recorded in
+        if feed is not None and getattr(feed, "random", False):
+            # a random_edges= feed rewrites the topology behind batch.edge_index on every fill, at a fixed capacity:
+            # only a model whose launches do not depend on the edge count can be recorded on it
+            from graphphysics.models.processors import EncodeProcessDecode
+
+            if isinstance(getattr(sim, "model", None), EncodeProcessDecode) or \
+                    getattr(sim, "edge_input_size", None) is not None or getattr(batch, "edge_attr", None) is not None:
+                raise ValueError("a random_edges= feed needs a model without edge_attr (EncodeTransformDecode): the "
+                                 "MGN path's launch shapes depend on the edge count")
+            if batch.edge_index is not feed.edge_index:
+                raise ValueError("with a random_edges= feed, batch.edge_index must be the feed's own edge_index tensor "
+                                 "(feed.edge_index): it is the handle of the topology the fill rebuilds")
         self.masks = list(masks)
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
@@ -195,8 +210,11 @@ class TrainStep:
         sc._last_lr = list(lrs)
 
     def _feed_mode(self):
-        """What the feed's fill draws: (frames drawn, angles drawn — None for a feed that does not rotate)."""
-        return (self.feed.random_frames, getattr(self.feed, "random_rotations", None))
+        """What the feed's fill draws: (frames drawn, angles drawn — None for a feed that does not rotate); for a feed
+        with random edges also whether its pairs are drawn."""
+        mode = (self.feed.random_frames, getattr(self.feed, "random_rotations", None))
+        pairs = getattr(self.feed, "random_pairs", None)
+        return mode if pairs is None else mode + (pairs,)
 
     def eager(self):
         self._check_replicas()

@@ -676,6 +676,44 @@ int mgn_world_topology_build(const float* pos, int64_t ld_pos /* >= 3 */,
                              int32_t* row_perm, int64_t* edge_index, int32_t* num_edges /* device */,
                              uint32_t* err_word, void* ws, size_t ws_bytes, mgn_stream_t stream);
 
+/* Random edges inside the step (the reference's BaseDataset._add_random_edges, dataset/dataset.py:104-137, the
+ * dataset.new_edges_ratio of every transformer config: per item, PyG's add_random_edge(p, force_undirected=True) adds
+ * "random jumps" to the adjacency that masks the attention). One call builds, with no host read-back, the topology of
+ *     mesh edges  ∪  both directions of every surviving random pair
+ * from a tensor of random bits, with the mesh, the result arrays and the capacity E_cap = E_m + N * max_new exactly as
+ * mgn_world_topology_build has them (see there).
+ *   Candidates. Graph g owns the candidates [cand_ptr[g], cand_ptr[g + 1]) of pairs [C, 2] (device int32, values
+ *     >= 0; cand_ptr: device int32 [B + 1], non-decreasing from 0 to C = num_candidates, fixed by the caller — the
+ *     Python side takes round(ratio * E_g) / 2 of them, as add_random_edge does, and none for a graph of fewer than
+ *     two nodes). Candidate c of graph g, with n_g nodes from lo_g on, has the endpoints a = lo_g + pairs[c][0] % n_g
+ *     and b = lo_g + pairs[c][1] % n_g.
+ *   Pass 1, per node i over its graph's candidates in order: a candidate with i as one endpoint, a != b, whose other
+ *     endpoint j is no mesh neighbour of i is live for i. A live candidate whose j is already in i's list is skipped;
+ *     else, when the list holds max_new entries, the candidate is dropped (flagged); else j is appended, c beside it.
+ *   Pass 2: i's new neighbours are the entries of its list whose candidate is not flagged, ascending.
+ *     An unordered pair survives exactly when its first candidate is unflagged, at both endpoints alike, so the
+ *     lists are symmetric. Dropping is the capacity policy: no error bit, the step goes on (the number of new
+ *     neighbours of a node is about Poisson; a rare overflow must not stop a training run).
+ *   *enabled (device int32): 0 makes every list empty, so the result is the mesh adjacency (validation).
+ *   A mesh neighbour outside [0, N) is clamped and NOT flagged here: the caller validates the mesh once. cand_ptr is
+ *     read on the device only; values outside [0, C] or out of order are clamped, every access stays in bounds.
+ * One memset node (the flags) and five launches (the endpoints of every candidate, one thread each; pass 1: one thread
+ * per node, the mapped candidates staged through LDS; pass 2: one thread per node, an insertion sort; then
+ * mgn_world_topology_build's scan and merge). Every grid is a function of N and num_candidates alone; no atomics, no allocation, no synchronisation: capturable, the same bits on every replay for the same
+ * pairs. ws: mgn_random_topology_workspace_bytes(N, max_new, num_candidates), caller-owned. N == 0 returns 0 without
+ * a launch. Before any launch, a nonzero status for NULL pointers, max_new outside [1, 64], a negative count, N > 0
+ * with B == 0, N or num_candidates > 2^30, E_m + N * max_new beyond int32, a workspace too small. The added symbols
+ * do not change MGN_ABI_VERSION; MGN_HAS_RANDOM_EDGES marks headers that declare them. */
+#define MGN_HAS_RANDOM_EDGES 1
+size_t mgn_random_topology_workspace_bytes(int64_t num_nodes, int32_t max_new, int64_t num_candidates);
+int mgn_random_topology_build(const int32_t* pairs /* device, [C, 2] */, const int32_t* cand_ptr /* device, [B + 1] */,
+                              int64_t num_candidates, const int32_t* graph_ptr, int32_t B, int64_t num_nodes,
+                              const int32_t* mesh_ptr, const int32_t* mesh_nbr, int64_t num_mesh_edges,
+                              int32_t max_new, const int32_t* enabled /* device, [1] */,
+                              int32_t* csc_src, int32_t* csc_dst, int32_t* csc_eid, int32_t* col_ptr, int32_t* row_ptr,
+                              int32_t* row_perm, int64_t* edge_index, int32_t* num_edges /* device */,
+                              void* ws, size_t ws_bytes, mgn_stream_t stream);
+
 /* Aneurysm features inside the feed (the reference's external/aneurysm.py build_features, which train.py hard-wires
  * as extra_node_features, then add_noise; coarse-aneurysm.json is written for this row). Frame rows are
  * [velocity (3), wall flag, ...], F >= 4; pos [N, 3] and node_type [N] are static, caller-owned and only read.
