@@ -131,7 +131,27 @@ struct ChainNodeBwdArgs {
     __bf16* d_aggr;             // dA0[:, 128:]
 };
 
+// node side of a block's data gradients (chain16_node_grad_kernel; what node_grad_kernel<__bf16, 128, 16> of
+// mgn_mlp.hip computes, bit for bit): dP = segment sums of dZ0 over the in- and out-edges, dx = dx_part +
+// dP_i·W0b + dP_j·W0c
+struct ChainNodeGradArgs {
+    const __bf16* dz0;          // [E][128] dZ of the edge layer 0, target-sorted edges
+    const int32_t* col_ptr;
+    const int32_t* row_ptr;
+    const int32_t* row_perm;
+    const __bf16* dx_part;      // [N][128] node-MLP part of dx
+    const __bf16* wt;           // W0bᵀ ‖ W0cᵀ: 2 x 32 transposed 16x16x32 fragments of the edge layer 0
+    __bf16* dP8;                // R8 [2][RP][128]: dP_i, dP_j (rows >= N zero)
+    __bf16* dx;                 // [N][128]
+    int64_t N, RP, ntiles;
+};
+
 bool chain_eligible(const mgn_mlp* m);
+// the edge MLP's layer 0 as chain16_node_grad reads it: bf16, [128 x 3·128]
+bool chain_node_grad_eligible(const mgn_mlp* edge);
+// dx_pair: dx written in the pair layout
+int chain16_node_grad(const mgn_mlp* edge, const mgn_topology* t, const void* dz0, const void* dx_part, void* dP8,
+                      void* dx, bool dx_pair, hipStream_t st);
 int chain16_edge_backward_parts(int64_t M);
 int chain16_node_backward_parts(int64_t M);
 bool chain_node_eligible(const mgn_mlp* m);  // bf16, 256 -> 128 -> 128, 4 layers, RMSNorm

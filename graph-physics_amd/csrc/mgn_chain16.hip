@@ -1695,6 +1695,210 @@ __global__ __launch_bounds__(NW * 64) void chain16_dense_bwd_kernel(ChainDenseBw
     }
 }
 
+// ---------------------------------------------------------------------------- node side of the data gradients
+// chain16_node_grad_kernel: node_grad_kernel<__bf16, 128, 16> (mgn_mlp.hip) in the tile-per-wave form of the
+// node kernels above. A lane sums one node's dZ0 rows in registers, in the B-operand form of
+// v_mfma_f32_16x16x32_bf16 (k-step s: 8 contiguous features, one 16-byte load per row and k-step), so no LDS
+// tile and no barrier sit between the sums and the MFMAs. The sums are taken by lane 4m + g (node m, features
+// 32s + 8g ..), so that the four lanes of a quad read 64 contiguous bytes of one row, and moved to the operand's
+// lane m + 16g by one lane permutation (summed in lane m + 16g itself a quad reads 16 bytes of four rows: the
+// launch took 19.1 us instead of 15.0, profiles/node_grad_chain_ab.txt). W0bᵀ ‖ W0cᵀ (64 KiB, the packed fragments as they stand) is copied into LDS once per
+// workgroup by LDS-DMA, issued after the first tile's loads. The fp32 sums take the same terms in the same
+// order as the generic kernel, and every accumulator sees its MFMA sequence (W0b k-steps 0..3, then W0c 0..3,
+// A = packed fragment, B = 8 contiguous k): the same bits.
+#ifndef MGN_NG_SG
+#define MGN_NG_SG 8  // edge rows per round trip and direction (16 VGPRs each)
+#endif
+constexpr int NG_SG = MGN_NG_SG;
+constexpr int NG_WELEMS = 2 * LFR * FRAG;            // 64 fragments
+constexpr size_t NG_LDS_W = (size_t)NG_WELEMS * 2;   // 64 KiB
+constexpr int NG_SROWS = SROWS + TR;                 // per wave: the transpose scratch, then its dx_part tile
+constexpr size_t NG_LDS = NG_LDS_W + (size_t)NW * NG_SROWS * SLD * 2;
+
+// this lane's 4 x 8 features of rows id[0 .. SG) of dz: one round trip
+__device__ __forceinline__ void ng_rows(u32x4 (&t)[NG_SG][4], const __bf16* dz, const int (&id)[NG_SG], int g) {
+#pragma unroll
+    for (int u = 0; u < NG_SG; ++u)
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            t[u][s] = *reinterpret_cast<const u32x4*>(dz + (int64_t)id[u] * H + 32 * s + 8 * g);
+}
+
+// acc += rows k + u < ke, in edge order (a row past the segment's end was loaded from its last edge: not added)
+__device__ __forceinline__ void ng_add(float (&acc)[4][8], const u32x4 (&t)[NG_SG][4], int k, int ke) {
+#pragma unroll
+    for (int u = 0; u < NG_SG; ++u)
+        if (k + u < ke) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const bf16x8 v = __builtin_bit_cast(bf16x8, t[u][s]);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) acc[s][e] += (float)v[e];
+            }
+        }
+}
+
+// the sums, taken by lane 4m + g, as the bf16 B operand of lane m + 16g
+__device__ __forceinline__ void ng_operand(const float (&acc)[4][8], bf16x8 (&B)[4], int lane) {
+    const int from = 4 * (4 * (lane & 15) + (lane >> 4));  // ds_bpermute's byte address of the source lane
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        bf16x8 v;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = (__bf16)acc[s][e];
+        u32x4 w = __builtin_bit_cast(u32x4, v);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w[i] = (unsigned)__builtin_amdgcn_ds_bpermute(from, (int)w[i]);
+        B[s] = __builtin_bit_cast(bf16x8, w);
+    }
+}
+
+// store_operand_r8 for an operand in the plain k order (element j of k-step s = feature 32s + 8g + j)
+__device__ __forceinline__ void ng_store_r8(const bf16x8 (&B)[4], __bf16* scr, __bf16* dst, int64_t tile, int lane) {
+    const int m = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        if ((m >> 3) == u) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) *reinterpret_cast<bf16x8*>(scr + (m & 7) * SLD + 32 * s + 8 * g) = B[s];
+        }
+        lds_fence();
+        unsigned rv[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) rv[q] = *reinterpret_cast<const unsigned*>(scr + q * SLD + 2 * lane);
+        bf16x8 c0, c1;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const bf16x2 p = __builtin_bit_cast(bf16x2, rv[q]);
+            c0[q] = p[0];
+            c1[q] = p[1];
+        }
+        __bf16* p = dst + (((int64_t)tile * 2 + u) * H + 2 * lane) * 8;
+        *reinterpret_cast<bf16x8*>(p) = c0;
+        *reinterpret_cast<bf16x8*>(p + 8) = c1;
+        lds_fence();
+    }
+}
+
+// P2: dx in the pair layout
+template <bool P2>
+__global__ __launch_bounds__(NW * 64) void chain16_node_grad_kernel(ChainNodeGradArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __bf16* W = reinterpret_cast<__bf16*>(smem);
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    __bf16* scr = reinterpret_cast<__bf16*>(smem + NG_LDS_W) + wave * NG_SROWS * SLD;
+    __bf16* dxs = scr + SROWS * SLD;  // [16][SLD]: the tile's dx_part rows
+    const int m = lane & 15, g = lane >> 4;
+    // the lane's node and feature group in the sums
+    const int sm = lane >> 2, sg = lane & 3;
+    const int64_t stride = (int64_t)gridDim.x * NW;
+    int64_t tile = (int64_t)wave * gridDim.x + blockIdx.x;
+    bf16x8 Bi[4], Bj[4];  // dP_i, dP_j of the wave's tile: the GEMM's B operands
+    // the weight copy: 64 pieces of 1 KiB (one wave instruction each), 8 per wave
+    auto stage = [&]() {
+#pragma unroll
+        for (int i = 0; i < NG_WELEMS / FRAG / NW; ++i) {
+            const int pc = wave + i * NW;
+            __builtin_amdgcn_global_load_lds(
+                (const __attribute__((address_space(1))) void*)(a.wt + pc * FRAG + lane * 8),
+                (__attribute__((address_space(3))) void*)(W + pc * FRAG), 16, 0, 0);
+        }
+    };
+    // Tile tl's loads and sums. Round trips: the segment bounds | the dx_part rows (whole rows, 16 lanes each,
+    // parked in the wave's LDS tile for the epilogue), the first group of row_perm ids and of in-edge rows (then
+    // the weight copy, STAGE) | further in-edge groups | the out-edge rows, group by group, the next group's ids
+    // under the current group's rows.
+    auto gather = [&](int64_t tl, auto stage_tag) {
+        const int g = sg;
+        const int64_t v = tl * TR + sm;
+        const bool ok = v < a.N;
+        const int64_t vr = clamp_row(v, a.N);
+        int kb0 = a.col_ptr[vr], ke0 = a.col_ptr[vr + 1], kb1 = a.row_ptr[vr], ke1 = a.row_ptr[vr + 1];
+        ke0 = ok ? ke0 : kb0;  // padding rows: empty segments, zero sums
+        ke1 = ok ? ke1 : kb1;
+        u32x4 dxl[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            dxl[p] = *reinterpret_cast<const u32x4*>(a.dx_part + clamp_row(tl * TR + 4 * p + (lane >> 4), a.N) * H +
+                                                     8 * (lane & 15));
+        int id[NG_SG];
+        u32x4 rows[NG_SG][4];
+        if (kb1 < ke1) {
+#pragma unroll
+            for (int u = 0; u < NG_SG; ++u) id[u] = a.row_perm[kb1 + u < ke1 ? kb1 + u : ke1 - 1];
+        }
+        if (kb0 < ke0) {
+            int k0[NG_SG];
+#pragma unroll
+            for (int u = 0; u < NG_SG; ++u) k0[u] = kb0 + u < ke0 ? kb0 + u : ke0 - 1;
+            ng_rows(rows, a.dz0, k0, g);
+        }
+        if constexpr (decltype(stage_tag)::value) stage();
+        float acc[4][8];
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[s][e] = 0.f;
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            *reinterpret_cast<u32x4*>(dxs + (4 * p + (lane >> 4)) * SLD + 8 * (lane & 15)) = dxl[p];
+        if (kb0 < ke0) {
+            ng_add(acc, rows, kb0, ke0);
+#pragma unroll 1
+            for (int k = kb0 + NG_SG; k < ke0; k += NG_SG) {
+                int kk[NG_SG];
+#pragma unroll
+                for (int u = 0; u < NG_SG; ++u) kk[u] = k + u < ke0 ? k + u : ke0 - 1;
+                ng_rows(rows, a.dz0, kk, g);
+                ng_add(acc, rows, k, ke0);
+            }
+        }
+        ng_operand(acc, Bi, lane);
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc[s][e] = 0.f;
+        if (kb1 < ke1) {
+#pragma unroll 1
+            for (int k = kb1; k < ke1; k += NG_SG) {
+                ng_rows(rows, a.dz0, id, g);
+#pragma unroll
+                for (int u = 0; u < NG_SG; ++u) id[u] = a.row_perm[k + NG_SG + u < ke1 ? k + NG_SG + u : ke1 - 1];
+                ng_add(acc, rows, k, ke1);
+            }
+        }
+        ng_operand(acc, Bj, lane);
+    };
+    if (tile < a.ntiles)
+        gather(tile, std::true_type{});
+    else
+        stage();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's weight copies landed
+    __syncthreads();
+    while (tile < a.ntiles) {
+        ng_store_r8(Bi, scr, a.dP8, tile, lane);  // the weight-gradient ring's operands
+        ng_store_r8(Bj, scr, a.dP8 + a.RP * H, tile, lane);
+        f4 acc[8];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) acc[t] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+#pragma unroll
+                for (int t = 0; t < 8; ++t)
+                    acc[t] = mfma16(*reinterpret_cast<const bf16x8*>(W + ((size_t)((b * 8 + t) * 4 + s) * 64 + lane) * 8),
+                                    b ? Bj[s] : Bi[s], acc[t]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+        for (int t = 0; t < 8; ++t) acc[t] += bf4(*reinterpret_cast<const u32x2*>(dxs + m * SLD + 16 * t + 4 * g));
+        store_rows<P2>(acc, scr, a.dx, tile, a.N, lane);
+        tile += stride;
+        if (tile < a.ntiles) gather(tile, std::false_type{});
+    }
+}
+
 }  // namespace
 
 // EdgeAgg scratch carve: full [N][128], head / tail [rows_pad(E)/16][128] (fp32, 256-byte aligned parts)
@@ -1918,6 +2122,35 @@ int chain16_node_backward(const mgn_mlp* m, int64_t M, const mgn_mlp_saved* sv, 
     *nparts = grid;
     ProfScope ps(PROF_BWD_NODE, st);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), LDS_TOTAL, st, a);
+    MGN_LAUNCH_CHECK();
+    return 0;
+}
+
+bool chain_node_grad_eligible(const mgn_mlp* edge) {
+    return edge->dtype == MGN_BF16 && edge->hidden == H && edge->in_dim == 3 * H && edge->wtpack != nullptr;
+}
+
+int chain16_node_grad(const mgn_mlp* edge, const mgn_topology* t, const void* dz0, const void* dx_part, void* dP8,
+                      void* dx, bool dx_pair, hipStream_t st) {
+    ChainNodeGradArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dz0 = reinterpret_cast<const __bf16*>(dz0);
+    a.col_ptr = t->col_ptr;
+    a.row_ptr = t->row_ptr;
+    a.row_perm = t->row_perm;
+    a.dx_part = reinterpret_cast<const __bf16*>(dx_part);
+    // layer 0 is the first pack: [W0aᵀ | W0bᵀ | W0cᵀ], 32 fragments each
+    a.wt = reinterpret_cast<const __bf16*>(edge->wtpack) + (int64_t)LFR * FRAG;
+    a.dP8 = reinterpret_cast<__bf16*>(dP8);
+    a.dx = reinterpret_cast<__bf16*>(dx);
+    a.N = t->num_nodes;
+    a.RP = rows_pad(a.N);
+    a.ntiles = a.RP / TR;  // every padded row: the R8 operands cover rows_pad(N)
+    if (a.ntiles == 0) return 0;
+    const auto kern = dx_pair ? chain16_node_grad_kernel<true> : chain16_node_grad_kernel<false>;
+    if (int e2 = set_lds_once((const void*)kern, NG_LDS)) return e2;
+    ProfScope ps(PROF_COMBINE, st);
+    hipLaunchKernelGGL(kern, dim3(node_grid(a.ntiles)), dim3(NW * 64), NG_LDS, st, a);
     MGN_LAUNCH_CHECK();
     return 0;
 }

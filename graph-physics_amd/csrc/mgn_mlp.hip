@@ -4508,6 +4508,36 @@ int launch_node_grad(const mgn_mlp* edge, const mgn_topology* t, const void* dz0
     return 0;
 }
 
+// The node side of a block's data gradients on chain16_node_grad_kernel (mgn_chain16.hip: persistent, one
+// wave per 16-node tile, W0bᵀ ‖ W0cᵀ in LDS) where it applies: bf16, h = 128, dP_i summed from dZ0 (no
+// edge-side aggregation scratch) — and, by measurement (profiles/node_grad_chain_ab.txt), on graphs of at least
+// NODE_GRAD_MIN_N nodes (two 16-node tiles per workgroup on the whole chip, so the weight copy is shared) and
+// E <= 8 N (the mean segment is one gather group: one round trip per direction). Smaller graphs (the plate:
+// N = 1,350) and denser ones (the k-hop-2 aneurysm mesh: E = 62 N, where a wave's eight-row groups are a long
+// serial chain) run no faster on it and keep the generic kernel. Both write the same bits.
+// Compile-time -DMGN_CHAIN_NODE_GRAD=0: always the generic kernel (A/B builds).
+// impl: 0 = that rule, 1 = the generic kernel, 2 = the chained kernel (an error where it does not apply).
+#ifndef MGN_CHAIN_NODE_GRAD
+#define MGN_CHAIN_NODE_GRAD 1
+#endif
+constexpr int64_t NODE_GRAD_MIN_N = 8192;
+static int node_grad_any(const mgn_mlp* edge, const mgn_topology* t, const void* dz0, const void* dx_part, void* dP8,
+                         void* dx, hipStream_t st, bool dx_pair, void* agg_scratch, int impl) {
+    const int H = edge->hidden;
+    const bool can = chain_node_grad_eligible(edge) && agg_scratch == nullptr;
+    MGN_REQUIRE(impl != 2 || can, "chained node_grad: bf16 h=128 edge MLP without edge-side aggregation only");
+    const bool pays = t->num_nodes >= NODE_GRAD_MIN_N && t->num_edges <= 8 * t->num_nodes;
+    if (impl == 2 || (impl == 0 && MGN_CHAIN_NODE_GRAD && can && pays))
+        return chain16_node_grad(edge, t, dz0, dx_part, dP8, dx, dx_pair, st);
+    int rc = 0;
+    if (edge->dtype == MGN_F32) {
+        MGN_DISPATCH_H(H, rc = (launch_node_grad<float, HH>(edge, t, dz0, dx_part, dP8, dx, st)))
+    } else {
+        MGN_DISPATCH_H(H, rc = (launch_node_grad<__bf16, HH>(edge, t, dz0, dx_part, dP8, dx, st, dx_pair, agg_scratch)))
+    }
+    return rc;
+}
+
 // =========================================================================== C ABI
 extern "C" {
 
@@ -5080,14 +5110,7 @@ static int block_backward_data_impl(const mgn_topology* t, const mgn_mlp* edge, 
         if (int r = mlp_bwd_any(edge, MODE_EDGE, E, &saved->edge, de_out, dt, H, oe, c.dz8, c.dsp, st)) return r;
     }
     // node side: dP = segment sums of dZ0, dx = dx_part + dP_i·W0b + dP_j·W0c
-    int rc = 0;
-    if (dt == MGN_F32) {
-        MGN_DISPATCH_H(H, rc = (launch_node_grad<float, HH>(edge, t, c.dz0, c.dx_part, c.dP8, dx, st)))
-    } else {
-        MGN_DISPATCH_H(H, rc = (launch_node_grad<__bf16, HH>(edge, t, c.dz0, c.dx_part, c.dP8, dx, st,
-                                                              flags & MGN_BWD_DX_PAIR, c.agg)))
-    }
-    return rc;
+    return node_grad_any(edge, t, c.dz0, c.dx_part, c.dP8, dx, st, flags & MGN_BWD_DX_PAIR, c.agg, 0);
 }
 
 int mgn_block_backward_data(const mgn_topology* t, const mgn_mlp* edge, const mgn_mlp* node, const void* x,
@@ -5273,6 +5296,19 @@ int mgn_block_backward_deferred3(const mgn_topology* t, const mgn_mlp* edge, con
     CallScope cs(opts);
     return mgn_block_backward_deferred2(t, edge, node, x, e, saved, dx_out, de_out, dx, de, edge_grads, node_grads, ws,
                                         ws_bytes, keep, keep_bytes, reduce2, flags, stream);
+}
+
+int mgn_node_grad(const mgn_topology* t, const mgn_mlp* edge, const void* dz0, const void* dx_part, void* dP8,
+                  void* dx, int32_t dx_pair, int32_t impl, const mgn_call_opts* opts, mgn_stream_t stream) {
+    MGN_REQUIRE(t && edge, "topology and edge MLP required");
+    MGN_REQUIRE(!opts || (opts->data_cus >= 0 && opts->wgrad_cus >= 0), "CU caps must be >= 0 (0 = no cap)");
+    MGN_REQUIRE(impl >= 0 && impl <= 2, "impl: 0 auto, 1 generic, 2 chained");
+    MGN_REQUIRE(edge->dtype == MGN_F32 || edge->dtype == MGN_BF16, "unsupported dtype");
+    MGN_REQUIRE(edge->in_dim == 3 * edge->hidden && edge->wtpack, "edge MLP of a block: layer 0 is [h x 3h], packed");
+    MGN_REQUIRE(!dx_pair || (edge->dtype == MGN_BF16 && edge->hidden == 128), "pair-layout dx: bf16 h=128 only");
+    MGN_REQUIRE(t->num_nodes == 0 || ((dz0 || t->num_edges == 0) && dx_part && dP8 && dx), "node_grad buffers NULL");
+    CallScope cs(opts);
+    return node_grad_any(edge, t, dz0, dx_part, dP8, dx, (hipStream_t)stream, dx_pair != 0, nullptr, impl);
 }
 
 int mgn_wgrad_reduce_many(const mgn_wgrad_reduce* reds, int32_t n, mgn_stream_t stream) {

@@ -156,6 +156,8 @@ EXPORTS = {
     "mgn_mlp_backward_deferred3": (_i32, [ctypes.POINTER(Mlp), _vp, _i32, _i64, _vp, _i64,
                                           ctypes.POINTER(MlpSaved), _vp, _i32, _vp, _i32, _vp, _vp, _sz, _vp, _sz,
                                           ctypes.POINTER(WgradReduce), _i32, ctypes.POINTER(CallOpts), _vp]),
+    "mgn_node_grad": (_i32, [ctypes.POINTER(Topology), ctypes.POINTER(Mlp), _vp, _vp, _vp, _vp, _i32, _i32,
+                             ctypes.POINTER(CallOpts), _vp]),
     "mgn_debug_wave_times": (_i32, [_i32, _vp, _i32]),
     "mgn_graph_attention_workspace_bytes": (_sz, [ctypes.POINTER(Topology), _i32, _i32, _i32]),
     "mgn_graph_attention_forward": (_i32, [ctypes.POINTER(Topology), _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp,
@@ -444,6 +446,19 @@ def mgn_dtype(torch_dtype):
 
 def torch_dtype(mdt):
     return torch.float32 if mdt == MGN_F32 else torch.bfloat16
+
+
+NODE_GRAD_AUTO, NODE_GRAD_GENERIC, NODE_GRAD_CHAINED = 0, 1, 2  # mgn_node_grad's impl
+
+
+def node_grad(topo, edge, dz0, dx_part, dP8, dx, dx_pair=False, impl=NODE_GRAD_AUTO, data_cus=0):
+    """mgn_node_grad: dP8 (R8 [2][rows padded to 64][h]: the segment sums of dz0 over in- and out-edges) and
+    dx = dx_part + dP_i·W0b + dP_j·W0c, written in place. topo: a Topology struct, edge: the edge MLP's Mlp
+    struct (its wtpack), the tensors contiguous and of the MLP's dtype; data_cus: the call's CU cap (0: none)."""
+    require_device(dx)
+    opts = CallOpts(int(data_cus), 0, None)
+    check(lib().mgn_node_grad(ctypes.byref(topo), ctypes.byref(edge), ptr(dz0), ptr(dx_part), ptr(dP8), ptr(dx),
+                              int(bool(dx_pair)), int(impl), ctypes.byref(opts), stream_ptr(dx.device)))
 
 
 def column_stats(x):

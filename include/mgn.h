@@ -340,6 +340,20 @@ int mgn_mlp_backward_deferred3(const mgn_mlp* m, const void* in, int32_t in_dtyp
                                float* grads, void* ws, size_t ws_bytes, void* keep, size_t keep_bytes,
                                mgn_wgrad_reduce* reduce1, int32_t flags, const mgn_call_opts* opts,
                                mgn_stream_t stream);
+/* The node side of a block's data gradients on its own (the last launch of mgn_block_backward_data):
+ *   dP_i[v] = Σ dz0[k]            over k in [col_ptr[v], col_ptr[v+1])      fp32 sums in edge order,
+ *   dP_j[v] = Σ dz0[row_perm[k]]  over k in [row_ptr[v], row_ptr[v+1])      rounded to the MLP's dtype
+ *   dx      = dx_part + dP_i·W0b + dP_j·W0c                                 W0 = [W0a | W0b | W0c]: edge layer 0
+ * dz0 [E, h] (target-sorted edges), dx_part and dx [N, h], dP8 [2][rows padded to 64][h] in the row-octet
+ * layout (dP_i, then dP_j; padded rows zero), all of edge->dtype; only edge->wtpack (layer 0) is read.
+ * dx_pair != 0 (bf16 h = 128): dx in the pair layout (MGN_BWD_DX_PAIR). impl: 0 = the kernel
+ * mgn_block_backward_data would launch, 1 = the generic kernel, 2 = the chained kernel (bf16, h = 128; a
+ * nonzero status elsewhere); both write the same bits. opts: as mgn_block_backward_deferred3 (data_cus).
+ * The added symbol does not change MGN_ABI_VERSION; MGN_HAS_NODE_GRAD marks headers that declare it. */
+#define MGN_HAS_NODE_GRAD 1
+int mgn_node_grad(const mgn_topology* t, const mgn_mlp* edge, const void* dz0, const void* dx_part,
+                  void* dP8, void* dx, int32_t dx_pair, int32_t impl, const mgn_call_opts* opts,
+                  mgn_stream_t stream);
 /* Diagnostics builds (MGN_STAMPS) only, else an error status: per-wave [start, end] s_memrealtime ticks
  * (100 MHz) of the last launch of a chained kernel kind (0 edge fwd, 1 edge bwd, 2 node fwd, 3 node
  * bwd), n <= 4096 waves in workgroup-major order. */

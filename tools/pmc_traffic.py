@@ -48,7 +48,8 @@ def kernel_class(name):
                      ("node_bwd_f32_chain_kernel", "bwd_node"),
                      ("mlp_wgrad_kernel", "wgrad_dense"), ("wgrad_ring_kernel", "wgrad"),
                      ("wgrad_ring_f32_kernel", "wgrad"), ("chain16_rew_kernel", "wgrad"),
-                     ("wgrad_reduce_kernel", "wgrad_reduce"), ("node_grad_kernel", "combine"),
+                     ("wgrad_reduce_kernel", "wgrad_reduce"), ("chain16_node_grad_kernel", "combine"),
+                     ("node_grad_kernel", "combine"),
                      ("node_proj_kernel", "proj"), ("adamw", "adamw"), ("pack_kernel", "pack")):
         if key in name:
             return cls
