@@ -41,6 +41,13 @@
 //                  in place, and their count into wc[i]. A pair survives exactly when its first candidate is
 //                  unflagged, which both endpoints see alike, so the lists are symmetric, as world_merge needs.
 // No atomics, no read-back; the grids are functions of N and of the candidate count, both fixed at construction.
+//
+// Both together (mgn.h, "World and random edges inside the step"; the reference's order: add_world_edges, then
+// _add_random_edges on top of the edge_index that left): world_search fills the world lists, random_search takes them
+// as a second exclusion list (a candidate that is a world edge of this build is skipped like a mesh edge: one more
+// binary search in the queued drain, over a list that is symmetric, so both endpoints see the same verdict),
+// random_filter sorts the random lists, and ONE scan and ONE merge run over three ascending, pairwise-disjoint lists
+// per node: mesh, world, random. A null third list leaves the scan and the merge of the two builds above as they were.
 #include "mgn_common.h"
 
 namespace {
@@ -137,11 +144,13 @@ __global__ __launch_bounds__(WORLD_THREADS) void world_search(
     }
 }
 
-// ptr[i] = Σ_{r < i} (mesh_deg[r] + wc[r]) for i in [0, N], into col_ptr and row_ptr; *num_edges = ptr[N]. One
-// workgroup: a thread sums a contiguous chunk, the chunk sums are scanned in LDS (Hillis–Steele), the thread
-// walks its chunk again. Integers: any order gives the same result.
+// ptr[i] = Σ_{r < i} (mesh_deg[r] + wc[r] + wc2[r]) for i in [0, N], into col_ptr and row_ptr; *num_edges = ptr[N].
+// wc2: the counts of a third list per node (the combined build), or null. One workgroup: a thread sums a contiguous
+// chunk, the chunk sums are scanned in LDS (Hillis–Steele), the thread walks its chunk again. Integers: any order gives
+// the same result.
 __global__ __launch_bounds__(WORLD_SCAN_THREADS) void world_scan(const int32_t* __restrict__ mesh_ptr, int E_m,
-                                                                 const int32_t* __restrict__ wc, int N, int E_cap,
+                                                                 const int32_t* __restrict__ wc,
+                                                                 const int32_t* __restrict__ wc2, int N, int E_cap,
                                                                  int32_t* __restrict__ col_ptr,
                                                                  int32_t* __restrict__ row_ptr,
                                                                  int32_t* __restrict__ num_edges) {
@@ -151,7 +160,7 @@ __global__ __launch_bounds__(WORLD_SCAN_THREADS) void world_scan(const int32_t* 
     int s = 0;
     for (int r = a; r < b; ++r) {
         const int m0 = clampi(mesh_ptr[r], 0, E_m);
-        s += clampi(mesh_ptr[r + 1], m0, E_m) - m0 + wc[r];
+        s += clampi(mesh_ptr[r + 1], m0, E_m) - m0 + wc[r] + (wc2 ? wc2[r] : 0);
     }
     part[threadIdx.x] = s;
     __syncthreads();
@@ -167,7 +176,7 @@ __global__ __launch_bounds__(WORLD_SCAN_THREADS) void world_scan(const int32_t* 
         col_ptr[r] = v;
         row_ptr[r] = v;
         const int m0 = clampi(mesh_ptr[r], 0, E_m);
-        run += clampi(mesh_ptr[r + 1], m0, E_m) - m0 + wc[r];
+        run += clampi(mesh_ptr[r + 1], m0, E_m) - m0 + wc[r] + (wc2 ? wc2[r] : 0);
     }
     if (threadIdx.x == WORLD_SCAN_THREADS - 1) {
         const int total = clampi(part[threadIdx.x], 0, E_cap);
@@ -180,12 +189,15 @@ __global__ __launch_bounds__(WORLD_SCAN_THREADS) void world_scan(const int32_t* 
 __global__ __launch_bounds__(256) void world_merge(const int32_t* __restrict__ mesh_ptr,
                                                    const int32_t* __restrict__ mesh_nbr, int E_m,
                                                    const int32_t* __restrict__ wl, const int32_t* __restrict__ wc,
-                                                   int W, int N, int E_cap, const int32_t* __restrict__ col_ptr,
+                                                   int W, const int32_t* __restrict__ wl2,
+                                                   const int32_t* __restrict__ wc2, int W2, int N, int E_cap,
+                                                   const int32_t* __restrict__ col_ptr,
                                                    int32_t* __restrict__ csc_src, int32_t* __restrict__ csc_dst,
                                                    int32_t* __restrict__ csc_eid, int32_t* __restrict__ row_perm,
                                                    int64_t* __restrict__ edge_index, uint32_t* __restrict__ err) {
-    // WORLD_MERGE_LANES lanes per node, lane s taking the node's edges s, s + 8, ...: the two lists share no value, so
-    // an entry's place in the merged list is its own index plus its rank in the OTHER list; no lane waits for another
+    // WORLD_MERGE_LANES lanes per node, lane s taking the node's edges s, s + 8, ...: the lists share no value, so an
+    // entry's place in the merged list is its own index plus its rank in every OTHER list; no lane waits for another.
+    // wl2 / wc2: a third ascending list per node, disjoint from the other two (the combined build), or null (no entry)
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int i = (int)(t / WORLD_MERGE_LANES), sub = (int)(t % WORLD_MERGE_LANES);
     if (i >= N) return;
@@ -194,16 +206,23 @@ __global__ __launch_bounds__(256) void world_merge(const int32_t* __restrict__ m
     const int32_t* ma = mesh_nbr + m0;
     const int32_t* wa = wl + (int64_t)i * W;
     const int wd = wc[i];
+    const int32_t* ra = wl2 ? wl2 + (int64_t)i * W2 : nullptr;
+    const int rd = wl2 ? wc2[i] : 0;
     const int base = col_ptr[i];
     bool bad = false;
-    for (int p = sub; p < md + wd; p += WORLD_MERGE_LANES) {
+    for (int p = sub; p < md + wd + rd; p += WORLD_MERGE_LANES) {
         int j, at;
         if (p < md) {
             j = ma[p];
             at = p + lower_bound_i32(wa, wd, j);
-        } else {
+            if (rd > 0) at += lower_bound_i32(ra, rd, j);
+        } else if (p < md + wd) {
             j = wa[p - md];
             at = p - md + lower_bound_i32(ma, md, j);
+            if (rd > 0) at += lower_bound_i32(ra, rd, j);
+        } else {
+            j = ra[p - md - wd];
+            at = p - md - wd + lower_bound_i32(ma, md, j) + lower_bound_i32(wa, wd, j);
         }
         if (j < 0 || j >= N) {  // a mesh neighbour outside [0, N): flagged, clamped, every access stays in bounds
             bad = true;
@@ -213,8 +232,9 @@ __global__ __launch_bounds__(256) void world_merge(const int32_t* __restrict__ m
         const int jm0 = clampi(mesh_ptr[j], 0, E_m);
         const int jmd = clampi(mesh_ptr[j + 1], jm0, E_m) - jm0;
         int e = col_ptr[j] + lower_bound_i32(mesh_nbr + jm0, jmd, i) + lower_bound_i32(wl + (int64_t)j * W, wc[j], i);
+        if (wl2) e += lower_bound_i32(wl2 + (int64_t)j * W2, wc2[j], i);
         e = clampi(e, 0, E_cap - 1);  // equal to its exact value unless a list overflowed (see MGN_ERR_WORLD_CAPACITY)
-        const int k = base + at;  // at <= md + wd - 1 for sorted, disjoint lists; guarded for anything else
+        const int k = base + at;  // at <= md + wd + rd - 1 for sorted, disjoint lists; guarded for anything else
         if (k >= 0 && k < E_cap) {
             csc_src[k] = j;
             csc_dst[k] = i;
@@ -258,8 +278,11 @@ __global__ __launch_bounds__(WORLD_THREADS) void random_map(const int32_t* __res
 __global__ __launch_bounds__(WORLD_THREADS) void random_search(
     const int2* __restrict__ mapped, const int32_t* __restrict__ cand_ptr, int C,
     const int32_t* __restrict__ graph_ptr, int B, int N, const int32_t* __restrict__ mesh_ptr,
-    const int32_t* __restrict__ mesh_nbr, int E_m, int W, const int32_t* __restrict__ enabled, int32_t* wl,
-    int32_t* wid, int32_t* __restrict__ wc, int32_t* __restrict__ flag) {
+    const int32_t* __restrict__ mesh_nbr, int E_m, const int32_t* __restrict__ xl, const int32_t* __restrict__ xc,
+    int XW, int W, const int32_t* __restrict__ enabled, int32_t* wl, int32_t* wid, int32_t* __restrict__ wc,
+    int32_t* __restrict__ flag) {
+    // xl / xc / XW: a second exclusion list per node, ascending, xc[i] entries at xl[i * XW ..] (the world neighbours of
+    // the combined build), or null / 0
     // the mapped endpoints (a, b) of a tile; (-1, -1) behind its end, so that a chunk may be read whole
     __shared__ int2 cand[RANDOM_TILE + RANDOM_CHUNK];
     __shared__ int32_t queue[RANDOM_QUEUE][WORLD_THREADS];  // per lane: the candidates that touch its node
@@ -274,14 +297,16 @@ __global__ __launch_bounds__(WORLD_THREADS) void random_search(
         c0 = clampi(cand_ptr[graph_of_row(graph_ptr, B, b0)], 0, C);
         c1 = clampi(cand_ptr[graph_of_row(graph_ptr, B, b1 - 1) + 1], c0, C);
     }
-    int q0 = 0, q1 = 0, m0 = 0, md = 0;
+    int q0 = 0, q1 = 0, m0 = 0, md = 0, xd = 0;
     if (active) {
         const int g = graph_of_row(graph_ptr, B, i);
         q0 = clampi(cand_ptr[g], c0, c1);
         q1 = clampi(cand_ptr[g + 1], q0, c1);
         m0 = clampi(mesh_ptr[i], 0, E_m);
         md = clampi(mesh_ptr[i + 1], m0, E_m) - m0;
+        if (xl) xd = clampi(xc[i], 0, XW);
     }
+    const int32_t* excl = xl ? xl + (int64_t)i * XW : nullptr;  // read only below xd, which is 0 for an inactive lane
     int32_t* mine = wl + (int64_t)i * W;
     int32_t* mine_id = wid + (int64_t)i * W;
     int cnt = 0, qn = 0;
@@ -297,6 +322,10 @@ __global__ __launch_bounds__(WORLD_THREADS) void random_search(
             const int j = q.x == i ? q.y : q.x;
             const int at = lower_bound_i32(mesh_nbr + m0, md, j);
             if (at < md && mesh_nbr[m0 + at] == j) continue;  // a mesh edge already
+            if (xd > 0) {
+                const int xa = lower_bound_i32(excl, xd, j);
+                if (xa < xd && excl[xa] == j) continue;  // an edge of the second list already (a world edge)
+            }
             bool seen = false;
             for (int k = 0; k < cnt; ++k) seen = seen || mine[k] == j;
             if (seen) continue;  // a repeat
@@ -420,12 +449,12 @@ int mgn_world_topology_build(const float* pos, int64_t ld_pos, const float* node
                        node_type, ld_type, graph_ptr, (int)B, n, mesh_ptr, mesh_nbr, e_m, radius * radius, (int)W, wl,
                        wc, err_word);
     MGN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(world_scan, dim3(1), dim3(WORLD_SCAN_THREADS), 0, st, mesh_ptr, e_m, wc, n, e_cap, col_ptr,
-                       row_ptr, num_edges);
+    hipLaunchKernelGGL(world_scan, dim3(1), dim3(WORLD_SCAN_THREADS), 0, st, mesh_ptr, e_m, wc,
+                       (const int32_t*)nullptr, n, e_cap, col_ptr, row_ptr, num_edges);
     MGN_LAUNCH_CHECK();
     hipLaunchKernelGGL(world_merge, dim3((unsigned)cdiv64(N * WORLD_MERGE_LANES, 256)), dim3(256), 0, st, mesh_ptr,
-                       mesh_nbr, e_m, wl, wc, (int)W, n, e_cap, col_ptr, csc_src, csc_dst, csc_eid, row_perm,
-                       edge_index, err_word);
+                       mesh_nbr, e_m, wl, wc, (int)W, (const int32_t*)nullptr, (const int32_t*)nullptr, 0, n, e_cap,
+                       col_ptr, csc_src, csc_dst, csc_eid, row_perm, edge_index, err_word);
     MGN_LAUNCH_CHECK();
     return 0;
 }
@@ -474,16 +503,92 @@ int mgn_random_topology_build(const int32_t* pairs, const int32_t* cand_ptr, int
         MGN_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(random_search, dim3(blocks), dim3(WORLD_THREADS), 0, st, mapped, cand_ptr, (int)C, graph_ptr,
-                       (int)B, n, mesh_ptr, mesh_nbr, e_m, (int)W, enabled, wl, wid, wc, flag);
+                       (int)B, n, mesh_ptr, mesh_nbr, e_m, (const int32_t*)nullptr, (const int32_t*)nullptr, 0, (int)W,
+                       enabled, wl, wid, wc, flag);
     MGN_LAUNCH_CHECK();
     hipLaunchKernelGGL(random_filter, dim3(blocks), dim3(WORLD_THREADS), 0, st, n, (int)W, (int)C, wl, wid, wc, flag);
     MGN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(world_scan, dim3(1), dim3(WORLD_SCAN_THREADS), 0, st, mesh_ptr, e_m, wc, n, e_cap, col_ptr,
-                       row_ptr, num_edges);
+    hipLaunchKernelGGL(world_scan, dim3(1), dim3(WORLD_SCAN_THREADS), 0, st, mesh_ptr, e_m, wc,
+                       (const int32_t*)nullptr, n, e_cap, col_ptr, row_ptr, num_edges);
     MGN_LAUNCH_CHECK();
     hipLaunchKernelGGL(world_merge, dim3((unsigned)cdiv64(N * WORLD_MERGE_LANES, 256)), dim3(256), 0, st, mesh_ptr,
-                       mesh_nbr, e_m, wl, wc, (int)W, n, e_cap, col_ptr, csc_src, csc_dst, csc_eid, row_perm,
-                       edge_index, sink);
+                       mesh_nbr, e_m, wl, wc, (int)W, (const int32_t*)nullptr, (const int32_t*)nullptr, 0, n, e_cap,
+                       col_ptr, csc_src, csc_dst, csc_eid, row_perm, edge_index, sink);
+    MGN_LAUNCH_CHECK();
+    return 0;
+}
+
+size_t mgn_world_random_topology_workspace_bytes(int64_t num_nodes, int32_t max_neighbors, int32_t max_new,
+                                                 int64_t num_candidates) {
+    const int64_t n = num_nodes < 1 ? 1 : num_nodes, w = max_neighbors < 1 ? 1 : max_neighbors;
+    const int64_t r = max_new < 1 ? 1 : max_new, c = num_candidates < 1 ? 1 : num_candidates;
+    // the world counts and lists; the random counts, lists and the candidate id beside every entry; the flags; the
+    // mapped endpoints
+    return al((size_t)n * 4) + al((size_t)n * (size_t)w * 4) + al((size_t)n * 4) + 2 * al((size_t)n * (size_t)r * 4) +
+           al((size_t)c * 4) + al((size_t)c * 8);
+}
+
+int mgn_world_random_topology_build(const float* pos, int64_t ld_pos, const float* node_type, int64_t ld_type,
+                                    const int32_t* pairs, const int32_t* cand_ptr, int64_t C,
+                                    const int32_t* graph_ptr, int32_t B, int64_t N, const int32_t* mesh_ptr,
+                                    const int32_t* mesh_nbr, int64_t E_m, double radius, int32_t W, int32_t R,
+                                    const int32_t* enabled, int32_t* csc_src, int32_t* csc_dst, int32_t* csc_eid,
+                                    int32_t* col_ptr, int32_t* row_ptr, int32_t* row_perm, int64_t* edge_index,
+                                    int32_t* num_edges, uint32_t* err_word, void* ws, size_t ws_bytes,
+                                    mgn_stream_t stream) {
+    const std::string who = "world_random_topology_build";
+    MGN_REQUIRE(N >= 0 && B >= 0 && E_m >= 0 && C >= 0, who + ": N, B, E_m and num_candidates must be >= 0");
+    MGN_REQUIRE(W >= 1, who + ": max_neighbors must be >= 1");
+    MGN_REQUIRE(R >= 1 && R <= RANDOM_MAX_NEW, who + ": max_new must lie in [1, 64]");
+    MGN_REQUIRE(radius > 0.0 && std::isfinite(radius), who + ": radius must be positive and finite");
+    MGN_REQUIRE(ld_pos >= 3, who + ": ld_pos is smaller than 3");
+    MGN_REQUIRE(ld_type >= 1, who + ": ld_type must be >= 1");
+    MGN_REQUIRE(N <= (1ll << 30) && E_m <= INT32_MAX && E_m + N * ((int64_t)W + (int64_t)R) <= INT32_MAX,
+                who + ": N must be <= 2^30 and E_m + N * (max_neighbors + max_new) must fit int32");
+    MGN_REQUIRE(C <= (1ll << 30), who + ": num_candidates must be <= 2^30");
+    MGN_REQUIRE(err_word != nullptr, who + ": NULL error word");
+    MGN_REQUIRE(enabled != nullptr, who + ": NULL enabled word");
+    MGN_REQUIRE(num_edges != nullptr && col_ptr != nullptr && row_ptr != nullptr, who + ": a null pointer argument");
+    MGN_REQUIRE(ws_bytes >= mgn_world_random_topology_workspace_bytes(N, W, R, C), who + ": workspace too small");
+    if (N == 0) return 0;
+    MGN_REQUIRE(B >= 1, who + ": nodes without a graph (B == 0)");
+    MGN_REQUIRE(pos && node_type && (pairs || C == 0) && cand_ptr && graph_ptr && mesh_ptr && (mesh_nbr || E_m == 0) &&
+                    csc_src && csc_dst && csc_eid && row_perm && edge_index && ws,
+                who + ": a null pointer argument");
+    hipStream_t st = (hipStream_t)stream;
+    char* w = reinterpret_cast<char*>(ws);
+    int32_t* wcW = reinterpret_cast<int32_t*>(w); w += al((size_t)N * 4);
+    int32_t* wlW = reinterpret_cast<int32_t*>(w); w += al((size_t)N * (size_t)W * 4);
+    int32_t* wcR = reinterpret_cast<int32_t*>(w); w += al((size_t)N * 4);
+    int32_t* wlR = reinterpret_cast<int32_t*>(w); w += al((size_t)N * (size_t)R * 4);
+    int32_t* wid = reinterpret_cast<int32_t*>(w); w += al((size_t)N * (size_t)R * 4);
+    int32_t* flag = reinterpret_cast<int32_t*>(w); w += al((size_t)(C < 1 ? 1 : C) * 4);
+    int2* mapped = reinterpret_cast<int2*>(w);
+    const int n = (int)N, e_m = (int)E_m, e_cap = (int)(E_m + N * ((int64_t)W + (int64_t)R));
+    const unsigned blocks = (unsigned)cdiv64(N, WORLD_THREADS);
+    hipLaunchKernelGGL(world_search, dim3(blocks), dim3(WORLD_THREADS), 0, st, pos, ld_pos, node_type, ld_type,
+                       graph_ptr, (int)B, n, mesh_ptr, mesh_nbr, e_m, radius * radius, (int)W, wlW, wcW, err_word);
+    MGN_LAUNCH_CHECK();
+    if (C > 0) {
+        MGN_TRY(hipMemsetAsync(flag, 0, (size_t)C * 4, st));
+        hipLaunchKernelGGL(random_map, dim3((unsigned)cdiv64(C, WORLD_THREADS)), dim3(WORLD_THREADS), 0, st, pairs,
+                           cand_ptr, (int)C, graph_ptr, (int)B, n, enabled, mapped);
+        MGN_LAUNCH_CHECK();
+    }
+    // the world lists of this build are the search's second exclusion list: a candidate that is a world edge is
+    // skipped like a mesh edge, at both endpoints alike (the world lists are symmetric)
+    hipLaunchKernelGGL(random_search, dim3(blocks), dim3(WORLD_THREADS), 0, st, mapped, cand_ptr, (int)C, graph_ptr,
+                       (int)B, n, mesh_ptr, mesh_nbr, e_m, (const int32_t*)wlW, (const int32_t*)wcW, (int)W, (int)R,
+                       enabled, wlR, wid, wcR, flag);
+    MGN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(random_filter, dim3(blocks), dim3(WORLD_THREADS), 0, st, n, (int)R, (int)C, wlR, wid, wcR, flag);
+    MGN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(world_scan, dim3(1), dim3(WORLD_SCAN_THREADS), 0, st, mesh_ptr, e_m, wcW, (const int32_t*)wcR, n,
+                       e_cap, col_ptr, row_ptr, num_edges);
+    MGN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(world_merge, dim3((unsigned)cdiv64(N * WORLD_MERGE_LANES, 256)), dim3(256), 0, st, mesh_ptr,
+                       mesh_nbr, e_m, wlW, wcW, (int)W, (const int32_t*)wlR, (const int32_t*)wcR, (int)R, n, e_cap,
+                       col_ptr, csc_src, csc_dst, csc_eid, row_perm, edge_index, err_word);
     MGN_LAUNCH_CHECK();
     return 0;
 }

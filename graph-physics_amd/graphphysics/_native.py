@@ -207,6 +207,10 @@ EXPORTS = {
     "mgn_random_topology_workspace_bytes": (_sz, [_i64, _i32, _i64]),
     "mgn_random_topology_build": (_i32, [_vp, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mgn_world_random_topology_workspace_bytes": (_sz, [_i64, _i32, _i32, _i64]),
+    "mgn_world_random_topology_build": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _i64, _vp, _vp, _i64,
+                                               _dbl, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _vp, _sz, _vp]),
     "mgn_feed_inflow_capacity": (_i32, []),
     "mgn_feed_inflow_stats": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp]),
     "mgn_feed_batch_aneurysm": (_i32, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, FeedRanges8,
@@ -801,6 +805,72 @@ def random_topology_build(pairs, cand_ptr, graph_ptr, mesh_ptr, mesh_nbr, max_ne
         ptr(pairs), ptr(cand_ptr), C, ptr(graph_ptr), B1 - 1, N, ptr(mesh_ptr), ptr(mesh_nbr), E_m, W, ptr(enabled),
         ptr(csc_src), ptr(csc_dst), ptr(csc_eid), ptr(col_ptr), ptr(row_ptr), ptr(row_perm), ptr(ei), ptr(num_edges),
         ptr(ws), ws.numel(), stream_ptr(dev)))
+
+
+def world_random_topology_workspace(N, max_neighbors, max_new, num_candidates, device):
+    """The scratch of one mgn_world_random_topology_build over N nodes and num_candidates pairs (uint8, caller-kept)."""
+    import torch
+
+    n = lib().mgn_world_random_topology_workspace_bytes(int(N), int(max_neighbors), int(max_new), int(num_candidates))
+    return torch.empty(max(int(n), 1), dtype=torch.uint8, device=device)
+
+
+def world_random_topology_build(pos, node_type, pairs, cand_ptr, graph_ptr, mesh_ptr, mesh_nbr, radius, max_neighbors,
+                                max_new, enabled, csc_src, csc_dst, csc_eid, col_ptr, row_ptr, row_perm, edge_index,
+                                num_edges, ws):
+    """The topology of mesh edges ∪ OBSTACLE–NORMAL pairs within `radius` ∪ the surviving random pairs of `pairs`
+    (mgn_world_random_topology_build; the rule: dataset.resident.world_random_topology_torch): the arguments of
+    world_topology_build and random_topology_build together, E_cap = E_m + N · (max_neighbors + max_new). Writes the
+    six arrays, edge_index int64 [2, E_cap] and num_edges int32 [1] in place on the current stream; a node over
+    max_neighbors flags the device error word (ValueError at the next poll), a node over max_new drops candidates.
+    Nothing is read back."""
+    import torch
+
+    require_device(pos)
+    dev, N, E_m, W, R = pos.device, pos.shape[0], mesh_nbr.numel(), int(max_neighbors), int(max_new)
+    if pos.dtype != torch.float32 or pos.dim() != 2 or pos.shape[1] < 3 or pos.stride(1) != 1:
+        raise ValueError("world_random_topology_build: pos must be an fp32 [N, >= 3] tensor with unit column stride")
+    t = node_type
+    if t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != N or t.device != dev or (N > 1 and t.stride(0) < 1):
+        raise ValueError(f"world_random_topology_build: node_type must be an fp32 [{N}] tensor (a view of any positive "
+                         "stride) on pos's device")
+    if pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.shape[1] != 2 or not pairs.is_contiguous() or \
+            pairs.device != dev:
+        raise ValueError("world_random_topology_build: pairs must be a contiguous int32 [C, 2] tensor on pos's device")
+    C = pairs.shape[0]
+    if W < 1:
+        raise ValueError(f"world_random_topology_build: max_neighbors {W} must be >= 1")
+    if not 1 <= R <= RANDOM_MAX_NEW:
+        raise ValueError(f"world_random_topology_build: max_new {R} must lie in [1, {RANDOM_MAX_NEW}]")
+    if not float(radius) > 0.0 or float(radius) == float("inf"):
+        raise ValueError(f"world_random_topology_build: radius {radius} must be positive and finite")
+    E_cap = E_m + N * (W + R)
+    B1 = graph_ptr.numel()
+    for name, a, n in (("graph_ptr", graph_ptr, None), ("cand_ptr", cand_ptr, B1), ("mesh_ptr", mesh_ptr, N + 1),
+                       ("mesh_nbr", mesh_nbr, E_m), ("enabled", enabled, 1),
+                       ("csc_src", csc_src, max(E_cap, 1)), ("csc_dst", csc_dst, max(E_cap, 1)),
+                       ("csc_eid", csc_eid, max(E_cap, 1)), ("row_perm", row_perm, max(E_cap, 1)),
+                       ("col_ptr", col_ptr, N + 1), ("row_ptr", row_ptr, N + 1), ("num_edges", num_edges, 1)):
+        if a.dtype != torch.int32 or a.dim() != 1 or not a.is_contiguous() or a.device != dev or \
+                (n is not None and a.numel() != n):
+            raise ValueError(f"world_random_topology_build: {name} must be a contiguous int32 "
+                             f"[{'B + 1' if n is None else n}] tensor on pos's device")
+    if B1 < 1 or (N > 0 and B1 < 2):
+        raise ValueError("world_random_topology_build: graph_ptr must hold B + 1 node offsets")
+    ei = edge_index
+    if ei.dtype != torch.int64 or tuple(ei.shape) != (2, max(E_cap, 1)) or not ei.is_contiguous() or ei.device != dev:
+        raise ValueError(f"world_random_topology_build: edge_index must be a contiguous int64 [2, {max(E_cap, 1)}] "
+                         "tensor on pos's device")
+    wsb = int(lib().mgn_world_random_topology_workspace_bytes(N, W, R, C))
+    if ws.dtype != torch.uint8 or ws.numel() < wsb or ws.device != dev:
+        raise ValueError(f"world_random_topology_build: ws must hold {wsb} bytes on pos's device")
+    ew = error_word(dev)
+    check(lib().mgn_world_random_topology_build(
+        ptr(pos), pos.stride(0) if N > 1 else max(pos.stride(0), 3), ptr(t), t.stride(0) if N > 1 else 1, ptr(pairs),
+        ptr(cand_ptr), C, ptr(graph_ptr), B1 - 1, N, ptr(mesh_ptr), ptr(mesh_nbr), E_m, float(radius), W, R,
+        ptr(enabled), ptr(csc_src), ptr(csc_dst), ptr(csc_eid), ptr(col_ptr), ptr(row_ptr), ptr(row_perm), ptr(ei),
+        ptr(num_edges), ew.ptr(), ptr(ws), ws.numel(), stream_ptr(dev)))
+    ew.arm()
 
 
 def feed_ranges8(ranges):

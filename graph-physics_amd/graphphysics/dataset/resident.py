@@ -68,9 +68,22 @@ which samples non-edges without replacement; this rule samples with replacement 
 repeats without redrawing, so it adds slightly fewer edges, by a fraction of about (1 + degree) / n_g + C_g / (n_g² / 2).
 The distribution follows PyG's; the draws for a seed do not.
 
+Both together (dynamic_edges= and random_edges= on one feed, given the same mesh edge_index, with one_topology=True —
+without it the two stay refused, as before: the capacity and the candidate rule below are the caller's choice, not a
+silent merge; plate.json with dataset.new_edges_ratio on): the reference builds a sample's adjacency in a fixed order — _apply_preprocessing runs
+add_world_edges on the sample's frame, _add_random_edges then adds its random jumps on top of the edge_index that
+left (dataset/h5_dataset.py:102-105) — and so does the fill: the world fill and the noise, the draw of pairs, then ONE
+mgn_world_random_topology_build from the noisy x, which rewrites one topology of the capacity E_m + N · (max_neighbors
++ max_new). world_random_topology_torch states the rule, the two rules above composed: a candidate that is a world
+edge of this build is discarded like a mesh edge, max_new caps the random neighbours only, max_neighbors the world
+neighbours (over it: MGN_ERR_WORLD_CAPACITY, as for dynamic_edges=). A stated deviation: the number of candidates stays
+round(ratio · E_g) // 2 over the MESH edges of graph g, where the reference counts the mesh plus the world edges of the
+sample; the count sizes tensors and launches of a recorded step and must be fixed at construction (on the plate batch
+the README measures, the world edges are 590–800 of about 120,000 edges, under 0.7 %).
+
 Not supported: `previous_data` outside aneurysm= (there it is the frame before the drawn one), dynamic_edges= and
 random_edges= for models with edge_attr (the MGN path: its launch shapes depend on the edge count; the edge_index given
-inside world_pos= stays static for the life of the feed), the two together, rotate= together with world_pos=, aneurysm=
+inside world_pos= stays static for the life of the feed), rotate= together with world_pos=, aneurysm=
 together with either, a wall flag that changes over time (aneurysm= takes the node types from frame 0), and trajectories
 of unequal length in one batch. batch.edge_index is written only by a dynamic_edges= or random_edges= feed (through its
 own tensor), batch.edge_attr only by a rotating feed that was given a clean edge_attr and by a world_pos= feed that was
@@ -481,6 +494,28 @@ def random_topology_torch(pairs, graph_ptr, mesh_edge_index, max_new, enabled=Tr
     return _topology_of_keys(torch.sort(torch.cat([mesh_key, new_key])).values, N)
 
 
+def world_random_topology_torch(pos, node_type, pairs, graph_ptr, mesh_edge_index, radius, max_neighbors, max_new,
+                                enabled=True, *, cand_ptr):
+    """mgn_world_random_topology_build's rule as torch ops on any device: the two rules above composed in the
+    reference's order (_apply_preprocessing runs add_world_edges on the sample's frame, _add_random_edges then adds
+    its random jumps on top of the edge_index that left; dataset/h5_dataset.py:102-105, dataset/dataset.py:104-137):
+      1. ei_w = world_topology_torch(pos, node_type, graph_ptr, mesh_edge_index, radius, max_neighbors)'s edge_index —
+         sorted, symmetric, unique, every edge inside one graph: check_mesh_edges' preconditions;
+      2. random_topology_torch(pairs, graph_ptr, ei_w, max_new, enabled, cand_ptr=cand_ptr).
+    So a candidate that is a self-pair, a mesh edge, a world edge of this build or a repeat is discarded; max_new caps
+    the new random neighbours only; a candidate dropped at one endpoint is removed at the other. enabled False: step
+    1's result. A node over max_neighbors raises the ValueError of MGN_ERR_WORLD_CAPACITY, a node over max_new nothing.
+    Returns (edge_index int64 [2, E], arrays) as both rules do.
+
+    A stated deviation from the reference: cand_ptr stays random_candidate_ptr(graph_ptr, MESH edges, ratio), where the
+    reference's add_random_edge counts round(p · E) over the mesh plus the world edges of the sample. The number of
+    candidates sizes launches and tensors of a recorded step, so it must be fixed at construction; on a plate batch
+    the world edges are under 1 % of the edges. What a feed with dynamic_edges= and random_edges= runs on CPU tensors,
+    and what the kernels are tested against."""
+    ei_w, _ = world_topology_torch(pos, node_type, graph_ptr, mesh_edge_index, radius, max_neighbors)
+    return random_topology_torch(pairs.to(pos.device), graph_ptr, ei_w, max_new, enabled, cand_ptr=cand_ptr)
+
+
 def check_rollout_columns(F, y_columns, out_columns, prev_columns, node_type_index):
     """The host-side preconditions of a resident rollout (ValueError): the model's output columns, the target
     columns and, when used, the previous-data columns have one width d; the output and previous-data ranges
@@ -699,9 +734,19 @@ class ResidentTrajectories:
     (int32 [C, 2], the candidates of the last fill), cand_ptr (int32 [B + 1]) and random_enabled (int32 [1]). fill
     draws pairs and calls build_random_edges(). set_random_edges(False) makes every build write the mesh adjacency
     (validation) without a new recording; set_pairs gives explicit pairs (tests). With the plain fill, with aneurysm=
-    and with a world_pos= that has no edge side; not with dynamic_edges=, a rotate= that carries an edge_attr, or a
-    world_pos= with an edge_index. Rollout.rollout_resident on such a feed does not rebuild: it runs on the topology of
-    the last build_random_edges(); for validation, feed.set_random_edges(False); feed.build_random_edges()."""
+    and with a world_pos= that has no edge side; not with a rotate= that carries an edge_attr or a world_pos= with an
+    edge_index. Rollout.rollout_resident on such a feed does not rebuild: it runs on the topology of the last
+    build_random_edges(); for validation, feed.set_random_edges(False); feed.build_random_edges().
+
+    one_topology: True with both dynamic_edges= and random_edges= (the two edge_index tensors must be equal; without
+    one_topology=True the two together raise ValueError, as they did before this mode existed): ONE topology
+    (models._engine.WorldRandomTopology) of the capacity E_cap = E_m + N · (max_neighbors + max_new) holds mesh ∪ world
+    ∪ random edges. fill does the world fill and the noise, draws pairs, then runs one build_edges on the noisy x
+    (world_random_topology_torch's rule). build_edges(pos, node_type) is the combined build, with the feed's current
+    pairs and random_enabled; build_random_edges() raises ValueError (it has no positions). set_random_edges, set_pairs
+    and current_edge_index work as above; a node over max_neighbors is an error, a node over max_new drops. Its
+    validation rollout: set_random_edges(False), then Rollout(..., feed=, world_edges="frame" | "prediction"), which
+    rebuilds every step and draws nothing."""
 
     ROTATE_KEYS = ("feature_indices", "edge_attr", "edge_index", "edge_feature_indices")
     WORLD_KEYS = ("world_pos_index_start", "world_pos_index_end", "node_type_index", "edge_index", "edge_attr_start")
@@ -710,7 +755,7 @@ class ResidentTrajectories:
     RANDOM_KEYS = ("edge_index", "ratio", "max_new")
 
     def __init__(self, traj, graph_ptr, y_columns, node_type_index, noise=None, frames="random", rotate=None,
-                 world_pos=None, aneurysm=None, dynamic_edges=None, random_edges=None):
+                 world_pos=None, aneurysm=None, dynamic_edges=None, random_edges=None, one_topology=False):
         if not torch.is_tensor(traj) or traj.dtype != torch.float32 or traj.dim() != 3 or not traj.is_contiguous():
             raise ValueError("traj must be a contiguous fp32 [T, N, F] tensor")
         T, N, F = traj.shape
@@ -738,9 +783,14 @@ class ResidentTrajectories:
                 raise ValueError("dynamic_edges= together with rotate= or aneurysm= is not supported")
             if world_pos is None:
                 raise ValueError("dynamic_edges= needs world_pos=: the world edges follow the world positions")
+        if one_topology and (dynamic_edges is None or random_edges is None):
+            raise ValueError("one_topology=True needs both dynamic_edges= and random_edges=")
         if random_edges is not None:
-            if dynamic_edges is not None:
-                raise ValueError("random_edges= together with dynamic_edges= is not supported: one topology per feed")
+            if dynamic_edges is not None and not one_topology:
+                # as before this mode existed: the two are not silently merged, the caller asks for it
+                raise ValueError("random_edges= together with dynamic_edges= is not supported: one topology per feed "
+                                 "(one_topology=True builds both into one, E_cap = E_m + N * (max_neighbors + "
+                                 "max_new))")
             if isinstance(rotate, dict) and rotate.get("edge_attr") is not None:
                 raise ValueError("random_edges= together with a rotate= that carries an edge_attr is not supported: "
                                  "models with edge_attr are not supported (their launch shapes depend on the edge "
@@ -762,15 +812,18 @@ class ResidentTrajectories:
             self._init_world(world_pos, gp)
         # dynamic_edges=: the world edges of every fill, as a topology rebuilt in place (see build_edges)
         self.dynamic = dynamic_edges is not None
+        # random_edges=: new long-range edges on every fill, as a topology rebuilt in place (see build_random_edges).
+        # With dynamic_edges= as well: ONE topology of mesh ∪ world ∪ random edges, rebuilt by build_edges
+        self.random = random_edges is not None
         self.topology, self.edge_index, self.num_edges_dev, self.topology_arrays = None, None, None, None
         if self.dynamic:
             self._init_dynamic(dynamic_edges, gp)
-        # random_edges=: new long-range edges on every fill, as a topology rebuilt in place (see build_random_edges)
-        self.random = random_edges is not None
         self.pairs, self.cand_ptr, self.random_enabled = None, None, None
         self.random_pairs = None  # None: no random edges; True: drawn on every fill; False: explicit pairs
         if self.random:
             self._init_random(random_edges, gp)
+        if self.dynamic and self.random:
+            self._init_world_random(gp)
         self.pos, self.node_type, self.inflow_stats, self.inflow_ptr, self.inflow_rows = None, None, None, None, None
         if self.aneurysm:
             self._init_aneurysm(aneurysm, gp)
@@ -864,6 +917,8 @@ class ResidentTrajectories:
             raise ValueError(f"dynamic_edges: E_m + N * max_neighbors = {E_cap} does not fit int32")
         self.radius, self.max_neighbors, self._gp_list = float(radius), W, gp
         self.mesh_edge_index = mesh.to(dev)
+        if self.random:
+            return  # with random_edges= as well: the one topology of both is made by _init_world_random
         if dev.type == "cuda":
             from graphphysics.models import _engine
 
@@ -874,18 +929,47 @@ class ResidentTrajectories:
             self.edge_index = torch.zeros(2, max(E_cap, 1), dtype=torch.int64)
             self.num_edges_dev = torch.zeros(1, dtype=torch.int32)
 
+    def _init_world_random(self, gp):
+        """dynamic_edges= and random_edges= together, after both were checked: one topology of the capacity E_cap =
+        E_m + N · (max_neighbors + max_new), rebuilt by build_edges."""
+        dev, N, mesh = self.traj.device, self.N, self.mesh_edge_index.cpu()
+        E_cap = mesh.shape[1] + N * (self.max_neighbors + self.max_new)
+        if E_cap > 2 ** 31 - 1:
+            raise ValueError(f"dynamic_edges + random_edges: E_m + N * (max_neighbors + max_new) = {E_cap} does not "
+                             "fit int32")
+        if dev.type == "cuda":
+            from graphphysics.models import _engine
+
+            self.topology = _engine.WorldRandomTopology(mesh, gp, N, self.radius, self.max_neighbors, self._cand_list,
+                                                        self.max_new, dev)
+            self.edge_index, self.num_edges_dev = self.topology.edge_index, self.topology.num_edges_dev
+            _engine.bind_topology(self.edge_index, self.topology)
+        else:
+            self.edge_index = torch.zeros(2, max(E_cap, 1), dtype=torch.int64)
+            self.num_edges_dev = torch.zeros(1, dtype=torch.int32)
+
     def build_edges(self, pos, node_type):
         """Rebuild the world edges from pos fp32 [N, >= 3] and node_type fp32 [N] (views of the batch's x): HIP
         tensors, mgn_world_topology_build into self.topology (device work only, capturable); CPU tensors,
         world_topology_torch into edge_index[:, :E], num_edges_dev and topology_arrays (a node over max_neighbors
-        raises at once there; on the device it flags the error word)."""
+        raises at once there; on the device it flags the error word). On a feed that has random_edges= as well: the
+        combined build, mgn_world_random_topology_build / world_random_topology_torch, with the feed's current pairs
+        and its random_enabled word (nothing is drawn here)."""
         if not self.dynamic:
             raise ValueError("build_edges: this feed was built without dynamic_edges=")
         if pos.is_cuda:
-            self.topology.build(pos, node_type)
+            if self.random:
+                self.topology.build(pos, node_type, self.pairs, self.random_enabled)
+            else:
+                self.topology.build(pos, node_type)
             return
-        ei, arrays = world_topology_torch(pos, node_type, self._gp_list, self.mesh_edge_index, self.radius,
-                                          self.max_neighbors)
+        if self.random:
+            ei, arrays = world_random_topology_torch(pos, node_type, self.pairs, self._gp_list, self.mesh_edge_index,
+                                                     self.radius, self.max_neighbors, self.max_new,
+                                                     bool(int(self.random_enabled)), cand_ptr=self._cand_list)
+        else:
+            ei, arrays = world_topology_torch(pos, node_type, self._gp_list, self.mesh_edge_index, self.radius,
+                                              self.max_neighbors)
         self.edge_index[:, :ei.shape[1]] = ei
         self.num_edges_dev.fill_(ei.shape[1])
         self.topology_arrays = arrays
@@ -907,6 +991,9 @@ class ResidentTrajectories:
             raise ValueError(f"random_edges max_new {W!r} must be an int in [1, {nat.RANDOM_MAX_NEW}]")
         dev, N = self.traj.device, self.N
         mesh = check_mesh_edges(re["edge_index"], gp, N)
+        if self.dynamic and not torch.equal(mesh, self.mesh_edge_index.cpu()):
+            raise ValueError("dynamic_edges= and random_edges= must be given the same edge_index: one mesh, one "
+                             "topology per feed")
         E_cap = mesh.shape[1] + N * W
         if E_cap > 2 ** 31 - 1:
             raise ValueError(f"random_edges: E_m + N * max_new = {E_cap} does not fit int32")
@@ -917,6 +1004,8 @@ class ResidentTrajectories:
         self.pairs = torch.zeros(self._cand_list[-1], 2, dtype=torch.int32, device=dev)
         self.random_enabled = torch.ones(1, dtype=torch.int32, device=dev)
         self.random_pairs = True
+        if self.dynamic:
+            return  # with dynamic_edges= as well: the one topology of both is made by _init_world_random
         if dev.type == "cuda":
             from graphphysics.models import _engine
 
@@ -934,6 +1023,9 @@ class ResidentTrajectories:
         for validation, feed.set_random_edges(False); feed.build_random_edges() leaves the mesh adjacency."""
         if not self.random:
             raise ValueError("build_random_edges: this feed was built without random_edges=")
+        if self.dynamic:
+            raise ValueError("build_random_edges: this feed has dynamic_edges= as well, its one topology needs the "
+                             "positions: use build_edges(pos, node_type)")
         if self.pairs.is_cuda:
             self.topology.build(self.pairs, self.random_enabled)
             return
@@ -1130,7 +1222,8 @@ class ResidentTrajectories:
         launches; CPU tensors: world_topology_torch), and batch.edge_index must be the feed's edge_index. With
         random_edges=: after any of these fills, the draw of pairs and build_random_edges (mgn_random_topology_build,
         a memset and five launches; CPU tensors: random_topology_torch), and batch.edge_index must be the feed's
-        edge_index."""
+        edge_index. With both: after the world fill, the draw of pairs and ONE build_edges on the noisy x
+        (mgn_world_random_topology_build, a memset and six launches; CPU tensors: world_random_topology_torch)."""
         x, y = batch.x, batch.y
         if x.device != self.traj.device or x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != self.N or \
                 x.shape[1] < self.Fx:
@@ -1196,8 +1289,10 @@ class ResidentTrajectories:
                     if wea is not None:
                         world_edge_features_torch(x, self._world_edge_index, wea, self.edge_attr_start)
                 if self.dynamic:  # add_world_edges reads the (noisy) world positions and the batch's node types
+                    if self.random and self.random_pairs:  # both: the draw, then ONE build of mesh ∪ world ∪ random
+                        self.pairs.random_(0, 2 ** 31 - 1)
                     self.build_edges(x, x[:, self.node_type_index + 3])
-                if self.random:
+                elif self.random:
                     self._fill_random()
                 return batch
             if rot and self.random_rotations:

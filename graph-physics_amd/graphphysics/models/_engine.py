@@ -7,6 +7,7 @@
                    edge_index tensor that stands for it.
 * RandomTopology — the same, rebuilt from a tensor of random bits (mesh edges ∪ random long-range pairs,
                    mgn_random_topology_build).
+* WorldRandomTopology — both in one topology (mesh ∪ world ∪ random edges, mgn_world_random_topology_build).
 * MlpSpec        — one build_mlp nn.Sequential (reference graphphysics/models/layers.py:77-113)
                    seen by the kernels: its Linear weights are packed into MFMA fragments, biases and
                    RMSNorm scale are read straight from the fp32 master parameters.
@@ -66,9 +67,9 @@ class GraphTopology:
 
 
 class _RebuiltTopology:
-    """What DynamicTopology and RandomTopology share: the static mesh adjacency as CSR, and the six arrays, edge_index
-    and the live edge count of a topology of the fixed capacity E_cap = E_m + N · per_node that a build rewrites in
-    place through raw pointers."""
+    """What DynamicTopology, RandomTopology and WorldRandomTopology share: the static mesh adjacency as CSR, and the
+    six arrays, edge_index and the live edge count of a topology of the fixed capacity E_cap = E_m + N · per_node that
+    a build rewrites in place through raw pointers."""
 
     def _init_arrays(self, mesh_edge_index, graph_ptr, num_nodes, per_node, device):
         dev = torch.device(device)
@@ -152,6 +153,43 @@ class RandomTopology(_RebuiltTopology):
         nat.random_topology_build(pairs, self.cand_ptr, self.graph_ptr, self.mesh_ptr, self.mesh_nbr, self.max_new,
                                   enabled_dev, self.csc_src, self.csc_dst, self.csc_eid, self.col_ptr, self.row_ptr,
                                   self.row_perm, self.edge_index, self.num_edges_dev, self._ws)
+
+
+class WorldRandomTopology(_RebuiltTopology):
+    """Both in one topology (mgn_world_random_topology_build, mgn.h "World and random edges inside the step"): the
+    static mesh adjacency, the world edges of the build's positions and, on top of those, the surviving pairs of a
+    tensor of random bits, by the rule of dataset.resident.world_random_topology_torch. Same attributes and `struct`
+    as DynamicTopology, over arrays of the fixed capacity E_cap = E_m + N · (max_neighbors + max_new); build() writes
+    through raw pointers, so bind_topology(self.edge_index, self) keeps get_topology and every recorded graph on this
+    object. Arguments as for DynamicTopology and RandomTopology."""
+
+    def __init__(self, mesh_edge_index, graph_ptr, num_nodes, radius, max_neighbors, cand_ptr, max_new, device):
+        cp = [int(v) for v in (cand_ptr.tolist() if torch.is_tensor(cand_ptr) else cand_ptr)]
+        if len(cp) != len(graph_ptr) or not cp or cp[0] != 0 or any(b < a for a, b in zip(cp, cp[1:])):
+            raise ValueError(f"cand_ptr must hold B + 1 = {len(graph_ptr)} non-decreasing candidate offsets from 0, "
+                             f"got {cp}")
+        if int(max_neighbors) < 1:
+            raise ValueError(f"max_neighbors {max_neighbors} must be >= 1")
+        if not 1 <= int(max_new) <= nat.RANDOM_MAX_NEW:
+            raise ValueError(f"max_new {max_new} must lie in [1, {nat.RANDOM_MAX_NEW}]")
+        self._init_arrays(mesh_edge_index, graph_ptr, num_nodes, int(max_neighbors) + int(max_new), device)
+        self.radius, self.max_neighbors = float(radius), int(max_neighbors)
+        self.max_new, self.num_candidates = int(max_new), cp[-1]
+        self.cand_ptr = torch.tensor(cp, dtype=torch.int32, device=self.device)
+        self._ws = nat.world_random_topology_workspace(self.num_nodes, self.max_neighbors, self.max_new,
+                                                       self.num_candidates, self.device)
+        nat.error_word(self.device)  # exists before any capture
+
+    def build(self, pos, node_type, pairs, enabled_dev):
+        """Rebuild from pos fp32 [N, >= 3] and node_type fp32 [N] (as DynamicTopology.build), pairs int32 [C, 2] and
+        enabled_dev int32 [1] (as RandomTopology.build; 0: mesh and world edges alone): one memset and six launches on
+        the current stream, capturable, nothing read back."""
+        if pairs.shape[0] != self.num_candidates:
+            raise ValueError(f"pairs must be int32 [{self.num_candidates}, 2], got {tuple(pairs.shape)}")
+        nat.world_random_topology_build(pos, node_type, pairs, self.cand_ptr, self.graph_ptr, self.mesh_ptr,
+                                        self.mesh_nbr, self.radius, self.max_neighbors, self.max_new, enabled_dev,
+                                        self.csc_src, self.csc_dst, self.csc_eid, self.col_ptr, self.row_ptr,
+                                        self.row_perm, self.edge_index, self.num_edges_dev, self._ws)
 
 
 # the block backward's weight-gradient halves run on a side stream, overlapped with the next block's

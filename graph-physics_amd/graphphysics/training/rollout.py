@@ -39,7 +39,10 @@ plate.json): the same modes say which positions the reference's add_world_edges 
 positions of frame start + s (the reference's validation: its edge_index is part of the dataset item), "prediction",
 the x the model is about to see — and one mgn_world_topology_build between the begin stage and the forward rebuilds
 the feed's bound topology in place, inside the recorded step. "off" is refused: there is no static adjacency to
-fall back to. batch.edge_index must be feed.edge_index; the steps' edge counts are kept in resident_num_edges.
+fall back to. batch.edge_index must be feed.edge_index; the steps' edge counts are kept in resident_num_edges. On a
+feed that has random_edges= as well, the same build_edges is mgn_world_random_topology_build with the feed's current
+pairs and random_enabled word: the rollout draws nothing, and after feed.set_random_edges(False) — what the reference's
+validation, which adds no random edges, amounts to — it equals the rollout of a dynamic_edges=-only feed.
 
 Aneurysm data (a feed built with aneurysm=): Rollout(..., acceleration=MODE) runs the same three stages with
 mgn_rollout_begin_aneurysm in front — the row [frame row (F) ‖ a − p ‖ pos ‖ mean, min, max ‖ node type] of the

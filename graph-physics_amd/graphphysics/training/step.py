@@ -45,7 +45,10 @@ three angles per graph, builds the rotation matrices and rotates x, y and — in
 edge_attr inside the same fill; switching set_rotations between drawn and explicit angles re-records as well.
 A feed built with random_edges= also draws its candidate pairs and rebuilds the topology behind batch.edge_index
 (which must be feed.edge_index) inside the fill, so every replay attends over new long-range edges; it is refused
-for a model that reads edge_attr, and switching set_pairs between drawn and explicit pairs re-records.
+for a model that reads edge_attr, and switching set_pairs between drawn and explicit pairs re-records. A feed built
+with dynamic_edges=, random_edges= and one_topology=True passes through the same checks: its fill does the world fill
+and the noise, the draw of pairs and one build of mesh ∪ world ∪ random edges; set_random_edges(False) needs no new
+recording, and a node over max_neighbors skips the update and raises at the next poll, as for dynamic_edges= alone.
 
 Validation errors flagged on libmgn's device error word (out-of-range edge_index, node types outside
 the one-hot range) surface as the reference's IndexError / RuntimeError at most one step late,

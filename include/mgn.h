@@ -728,6 +728,48 @@ int mgn_random_topology_build(const int32_t* pairs /* device, [C, 2] */, const i
                               int32_t* row_perm, int64_t* edge_index, int32_t* num_edges /* device */,
                               void* ws, size_t ws_bytes, mgn_stream_t stream);
 
+/* World and random edges inside the step: both of the above in one topology, in the reference's order —
+ * _apply_preprocessing runs add_world_edges on the sample's frame, _add_random_edges then adds its random jumps on top
+ * of the edge_index that left (dataset/h5_dataset.py:102-105). One call builds, with no host read-back, the topology of
+ *     mesh edges  ∪  both directions of every world pair  ∪  both directions of every surviving random pair
+ * with the capacity E_cap = E_m + N * (max_neighbors + max_new); the mesh, the result arrays, the pair rule and
+ * MGN_ERR_WORLD_CAPACITY are mgn_world_topology_build's, the candidates, both passes, *enabled and the dropping
+ * policy mgn_random_topology_build's, with one addition: a candidate whose other endpoint is a WORLD neighbour of
+ * this build is not live either (like a mesh edge, it is discarded without a redraw). max_new caps the new random
+ * neighbours only. The world lists are symmetric, so both endpoints see the same verdict and the random lists stay
+ * symmetric. cand_ptr is the caller's, fixed at construction (the Python side counts it from the mesh edges alone; the
+ * reference counts round(p * E) over mesh plus world edges of the sample, a number that changes per sample and so
+ * cannot size a recorded launch).
+ *   *enabled == 0: the result equals mgn_world_topology_build's on the same inputs, entry for entry (the six arrays,
+ *     the first *num_edges columns of edge_index, *num_edges); only E_cap, the distance of edge_index's rows, differs.
+ *   A node over max_neighbors sets MGN_ERR_WORLD_CAPACITY as above: the topology is then unspecified (the truncated
+ *     world lists need not be symmetric), every index written stays inside its array and inside [0, N). A mesh
+ *     neighbour outside [0, N) sets MGN_ERR_EDGE_INDEX and is clamped.
+ * One memset node and six launches: mgn_world_topology_build's search; the endpoints of every candidate; pass 1 with
+ * the world lists as a second exclusion list (one more binary search per queued hit); pass 2; ONE scan over the three
+ * degrees; ONE merge of three ascending, pairwise-disjoint lists per node (an entry's place is its own index plus its
+ * rank in each of the other two; the id of edge (j -> i) is col_ptr[j] plus the rank of i in each of j's three lists).
+ * Every grid is a function of N and num_candidates alone; no atomics beyond the OR into *err_word, no allocation, no
+ * synchronisation: capturable. ws: mgn_world_random_topology_workspace_bytes(N, max_neighbors, max_new,
+ * num_candidates), caller-owned. N == 0 returns 0 without a launch. Before any launch, a nonzero status for what
+ * either build refuses, with E_m + N * (max_neighbors + max_new) beyond int32 in place of their capacity checks. The
+ * added symbols do not change MGN_ABI_VERSION; MGN_HAS_WORLD_RANDOM_EDGES marks headers that declare them. */
+#define MGN_HAS_WORLD_RANDOM_EDGES 1
+size_t mgn_world_random_topology_workspace_bytes(int64_t num_nodes, int32_t max_neighbors, int32_t max_new,
+                                                 int64_t num_candidates);
+int mgn_world_random_topology_build(const float* pos, int64_t ld_pos /* >= 3 */,
+                                    const float* node_type, int64_t ld_type,
+                                    const int32_t* pairs /* device, [C, 2] */,
+                                    const int32_t* cand_ptr /* device, [B + 1] */, int64_t num_candidates,
+                                    const int32_t* graph_ptr, int32_t B, int64_t num_nodes,
+                                    const int32_t* mesh_ptr, const int32_t* mesh_nbr, int64_t num_mesh_edges,
+                                    double radius, int32_t max_neighbors, int32_t max_new,
+                                    const int32_t* enabled /* device, [1] */,
+                                    int32_t* csc_src, int32_t* csc_dst, int32_t* csc_eid, int32_t* col_ptr,
+                                    int32_t* row_ptr, int32_t* row_perm, int64_t* edge_index,
+                                    int32_t* num_edges /* device */, uint32_t* err_word, void* ws, size_t ws_bytes,
+                                    mgn_stream_t stream);
+
 /* Aneurysm features inside the feed (the reference's external/aneurysm.py build_features, which train.py hard-wires
  * as extra_node_features, then add_noise; coarse-aneurysm.json is written for this row). Frame rows are
  * [velocity (3), wall flag, ...], F >= 4; pos [N, 3] and node_type [N] are static, caller-owned and only read.
